@@ -29,7 +29,11 @@ two-stream step; `roofline_chain` = the same byte definition per whole stage; `k
 `value` is wall time over steps whose K and V chains OVERLAP on two HIP streams; `stage_ms` / `roofline_chain` are measured in
 a separate serial pass (one chain at a time), so their sum is larger than `ms_per_step`.
 
-Launch:  python bench.py [--gpus N --steps K --warmup W]      (N > 1 via torch.distributed.run, one rank per GPU)
+A plain run sets up, warms up, times K steps and prints the headline line (`value`, `ms_per_step`, the workload); everything
+described above except `value` -- stages, rooflines, kernels, traffic, sharding, attention, cpu_baseline, block boundary and
+decode -- is measured with --full only.  --dump-outputs DIR writes what the last timed step returned (see dump_outputs).
+
+Launch:  python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]   (N > 1 via torch.distributed.run)
 """
 import argparse
 import hashlib
@@ -56,6 +60,8 @@ CONFIGS = {
 }
 D = 128
 HBM_PEAK_GBS = 8000.0  # MI355X spec (/opt/skills/guides/MI355X_MICROARCH.md); ~6300 GB/s is what a plain copy reaches
+DUMP_BUDGET = 48 << 20  # bytes of all --dump-outputs files together
+DUMP_SEED = 0
 
 
 def parse():
@@ -84,7 +90,17 @@ def parse():
     ap.add_argument("--exchange", default="both", choices=("peer", "collective", "both"),
                     help="world > 1, decode leg: the head-shard exchange -- 'peer' = stores into hipIpc-mapped peer memory "
                          "(gear_xchg_allgather), 'collective' = all_gather_into_tensor (RCCL), 'both' = one decode leg each")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, everything else the line can carry: the other V selection's step time, per-stage and "
+                         "per-kernel timings, rooflines, shard parity, attention, CPU baseline, block boundary, decode tokens/s "
+                         "(off: the line holds the headline figure only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (payloads, decompressed K^T / V) to DIR/<name>.npy as float32 / "
+                         "float64; arrays larger than the per-array share of %d MB are a fixed seeded sample" % (DUMP_BUDGET >> 20))
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def lib_sha256():
@@ -94,6 +110,39 @@ def lib_sha256():
         for chunk in iter(lambda: f.read(1 << 20), b""):
             h.update(chunk)
     return h.hexdigest()
+
+
+def dump_outputs(path, out, prefix=""):
+    """--dump-outputs: the arrays the last timed step returned -- per group of layers the K and V payloads (codes, scale / zero
+    point, low-rank factors, outlier lists) and the decompressed K^T and V -- as <prefix><name>.npy.  Floating-point arrays are
+    written as float32, integer arrays as float64 (exact for the int32 code words).  An array of more elements than its share of
+    DUMP_BUDGET is written as the elements at a fixed sorted sample of flat positions (seed DUMP_SEED, the same for every array of
+    that size), so that the files of two runs with the same arguments compare element for element."""
+    import numpy as np
+    groups = out if isinstance(out, list) else [out]
+    arrays = []
+    for gi, (pk, pv, kr, vr) in enumerate(groups):
+        g = "" if len(groups) == 1 else f"g{gi}_"
+        arrays += [(f"{g}k_decompressed_t", kr), (f"{g}v_decompressed", vr)]
+        for kind, p in (("k", pk), ("v", pv)):
+            for field in ("code", "scale", "mn", "P", "Q", "oidx", "oval"):
+                if getattr(p, field) is not None:
+                    arrays.append((f"{g}{kind}_{field}", getattr(p, field)))
+    cap = min(1 << 18, DUMP_BUDGET // (8 * len(arrays)))
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays:
+        flat = t.reshape(-1)
+        if t.dtype == torch.uint16:           # (few ops take uint16 on the device: gather its bits as int16)
+            flat = flat.view(torch.int16)
+        if flat.numel() > cap:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(flat.numel(), cap, replace=False))
+            a = flat[torch.from_numpy(idx).to(flat.device)].cpu().numpy()
+        else:
+            a = flat.cpu().numpy().reshape(tuple(t.shape))
+        if t.dtype == torch.uint16:
+            a = a.view(np.uint16)
+        a = a.astype(np.float32 if t.dtype.is_floating_point else np.float64)
+        np.save(os.path.join(path, prefix + name + ".npy"), a)
 
 
 def cpu_baseline(cfg):
@@ -602,6 +651,31 @@ def main():
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, f"rank{rank}_" if world > 1 else "")
+    n = K.numel()                                 # elements per tensor kind, this rank
+    fp16_bytes_job = 2 * n * 2 * world            # K + V, whole job
+    value = 2 * fp16_bytes_job * args.steps / dt / 1e9   # through compress + through decompress
+    line = {
+        "metric": "KV compress+decompress GB/s (fp16 KV bytes through compress + through decompress per second)",
+        "value": value, "unit": "GB/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        # untimed steps IN FRONT of the `warmup` steps of the contract (device clocks / power state; --prewarm-s 0 = none)
+        "prewarm_steps": prewarm_steps, "prewarm_s": round(prewarm_seconds, 3),
+        "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
+        "dtype": "f32 arithmetic on fp16 data, int%d payload" % bits, "data": "synthetic",
+        "config": {"workload": f"{cfg['model']} KV cache, {layers} layers x {H} KV heads x T={T} x D={D}, "
+                               f"{bits}-bit g={group} per-channel K / per-token V + rank-{rnk} (loop {loop}) + "
+                               f"{sparsity * 100:.0f}% outliers (BASELINE configs[{cfg['idx']}])",
+                   "parallelism": f"head-shard x{world}", "k_outliers_per_side": [k_key, k_val],
+                   "streams": args.streams, "key_path": key_path if key_path != "auto" else
+                   ("fused" if C.key_fused_supported(T, D, group, bits, k_key) and C._KEY_PATH_DEFAULT == "auto" else C._KEY_PATH_DEFAULT)},
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(line))
+        if dist is not None:
+            dist.destroy_process_group()
+        return
 
     # sharded legs: the same timed loop once more with the OTHER V selection (k / N inside the shard's own heads, rounds 1-3) --
     # `value` is the exact selection (the algorithm of N = 1), `value_per_shard_selection` stands beside it
@@ -622,10 +696,7 @@ def main():
             dt_other = float(t.item())
         comp_v = comp_v_exact
     del out
-    n = K.numel()                                 # elements per tensor kind, this rank
     BH = layers * Hl
-    fp16_bytes_job = 2 * n * 2 * world            # K + V, whole job
-    value = 2 * fp16_bytes_job * args.steps / dt / 1e9   # through compress + through decompress
 
     # ---- per-stage GPU time (HIP events on the launch stream): a dedicated serial pass, outside the timed region
     step_serial()                                # (untimed: first main-stream allocations of the outputs)
@@ -862,19 +933,8 @@ def main():
 
     res = None
     if rank == 0:
-        res = {
-            "metric": "KV compress+decompress GB/s (fp16 KV bytes through compress + through decompress per second)",
-            "value": value, "unit": "GB/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            # untimed steps IN FRONT of the `warmup` steps of the contract (device clocks / power state; --prewarm-s 0 = none)
-            "prewarm_steps": prewarm_steps, "prewarm_s": round(prewarm_seconds, 3),
-            "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
-            "dtype": "f32 arithmetic on fp16 data, int%d payload" % bits, "data": "synthetic",
-            "config": {"workload": f"{cfg['model']} KV cache, {layers} layers x {H} KV heads x T={T} x D={D}, "
-                                   f"{bits}-bit g={group} per-channel K / per-token V + rank-{rnk} (loop {loop}) + "
-                                   f"{sparsity * 100:.0f}% outliers (BASELINE configs[{cfg['idx']}])",
-                       "parallelism": f"head-shard x{world}", "k_outliers_per_side": [k_key, k_val],
-                       "streams": args.streams, "key_path": key_path if key_path != "auto" else
-                       ("fused" if C.key_fused_supported(T, D, group, bits, k_key) and C._KEY_PATH_DEFAULT == "auto" else C._KEY_PATH_DEFAULT)},
+        res = dict(line)
+        res.update({
             "compress_GBps": fp16_bytes_job / ((stages["k_compress"] + stages["v_compress"]) * 1e-3) / 1e9,
             "decompress_GBps": fp16_bytes_job / ((stages["k_decompress"] + stages["v_decompress"]) * 1e-3) / 1e9,
             "stage_ms": stages,
@@ -888,7 +948,7 @@ def main():
             "roofline": roofline,
             "roofline_chain": chain,
             "kernels": kernels,
-        }
+        })
         if shard_info is not None:
             if dt_other is not None:
                 shard_info["per_shard"]["value_GBps"] = 2 * fp16_bytes_job * args.steps / dt_other / 1e9

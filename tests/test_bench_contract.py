@@ -146,3 +146,66 @@ def test_round5_sharded_lines_report_both_selections_and_shard_parity():
     d = json.load(open(os.path.join(ROOT, "profiles", "r5_bench_2rank_one_gpu.json")))
     assert d["n_gpus"] == 2 and d["sharding"]["shard_parity"] is True and d["sharding"]["v_selection"] == "exact"
     assert d["decode"]["exchange_default"] == "collective" and set(d["decode"]["exchange_modes"]) == {"peer", "collective"}
+
+
+def test_bench_plain_run_options(monkeypatch):
+    """A plain run is the headline line only; --full adds the rest, --dump-outputs writes the last step's outputs, --steps >= 1."""
+    import sys
+    if ROOT not in sys.path:
+        sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "3"])
+    a = bench.parse()
+    assert a.steps == 7 and a.warmup == 3 and a.full is False and a.dump_outputs is None
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "d"
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        bench.parse()
+
+
+def test_bench_dump_outputs_is_seeded_and_bounded(tmp_path):
+    """--dump-outputs on host tensors of the payload layout (compress.py): float32 / float64 only, whole arrays below the per-array
+    share of the budget, a seeded sample of the same positions above it, identical files from identical outputs, <= 64 MB."""
+    import sys
+    import numpy as np
+    import torch
+    if ROOT not in sys.path:
+        sys.path.insert(0, ROOT)
+    import bench
+    from gear_amd.compress import Payload
+    g = torch.Generator().manual_seed(0)
+    L, H, T, D, r, k = 1, 4, 4096, 128, 8, 40
+
+    def payload(kind, rows, per_row):
+        return Payload(kind, (L, H, T, D), 2, 64, 1,
+                       code=torch.randint(-2 ** 31, 2 ** 31 - 1, (rows, per_row // 16), generator=g, dtype=torch.int32),
+                       scale=torch.rand((rows, per_row // 64), generator=g), mn=torch.rand((rows, per_row // 64), generator=g),
+                       P=torch.rand((L, H, D, r), generator=g).half(), Q=torch.rand((L, H, T, r), generator=g).half(),
+                       oidx=torch.randint(0, 65535, (rows, 2 * k), generator=g, dtype=torch.int32).to(torch.uint16),
+                       oval=torch.rand((rows, 2 * k), generator=g).half(), k_out=k)
+
+    out = (payload("k", L * H * D, T), payload("v", L * H * T, D), torch.rand((L, H, D, T), generator=g).half(),
+           torch.rand((L, H, T, D), generator=g).half())
+    bench.dump_outputs(str(tmp_path / "a"), out)
+    bench.dump_outputs(str(tmp_path / "b"), out)
+    files = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert files == sorted([f"{kd}_{f}.npy" for kd in "kv" for f in ("code", "scale", "mn", "P", "Q", "oidx", "oval")] +
+                           ["k_decompressed_t.npy", "v_decompressed.npy"])
+    assert sum((tmp_path / "a" / f).stat().st_size for f in files) <= 64 << 20
+    for f in files:
+        x, y = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert x.dtype in (np.float32, np.float64) and np.array_equal(x, y), f
+    P = np.load(tmp_path / "a" / "k_P.npy")                       # small: whole, in its shape
+    assert P.shape == (L, H, D, r) and np.array_equal(P, out[0].P.float().numpy())
+    kt = np.load(tmp_path / "a" / "k_decompressed_t.npy")        # 2M elements: the seeded sample
+    idx = np.sort(np.random.default_rng(bench.DUMP_SEED).choice(out[2].numel(), kt.size, replace=False))
+    assert kt.size < out[2].numel() and np.array_equal(kt, out[2].reshape(-1).float().numpy()[idx])
+    code = np.load(tmp_path / "a" / "v_code.npy")                # int32 code words: float64, exact
+    assert code.dtype == np.float64 and np.array_equal(code, out[1].code.numpy().reshape(code.shape).astype(np.float64))
+    u16 = [p.oidx.view(torch.int16).numpy().view(np.uint16) for p in out[:2]]     # positions above 2^15 included
+    assert np.array_equal(np.load(tmp_path / "a" / "k_oidx.npy"), u16[0])            # whole
+    oidx = np.load(tmp_path / "a" / "v_oidx.npy")                                    # sampled
+    idx = np.sort(np.random.default_rng(bench.DUMP_SEED).choice(u16[1].size, oidx.size, replace=False))
+    assert oidx.size < u16[1].size and np.array_equal(oidx, u16[1].reshape(-1)[idx])

@@ -2,6 +2,7 @@
 # A/B of bench.py on ONE box: each argument is an environment assignment list ("GEAR_KFUSED_MAIN=1", "" = defaults); every
 # configuration runs $REPS times, interleaved.  usage: tools/bench_ab.sh "" "GEAR_KFUSED_MAIN=1"
 REPS=${REPS:-2}
+BENCH_ARGS="--full ${BENCH_ARGS:-}"     # (the lines are read for stage_ms: a --full field)
 mkdir -p gpurun_out
 for r in $(seq $REPS); do
   i=0

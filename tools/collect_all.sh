@@ -12,11 +12,11 @@ tools/collect_profiles.sh $TAG > gpurun_out/collect_$TAG.log 2>&1
 GEAR_PROF_CONFIG=c2 tools/collect_profiles.sh ${TAG}c2 --config c2 > gpurun_out/collect_${TAG}c2.log 2>&1
 python tools/publish_profiles.py $TAG c3
 python tools/publish_profiles.py ${TAG}c2 c2
-python bench.py 2> $PUB/bench.err | tail -1 > profiles/${TAG}_bench_line.json
-python bench.py --config c2 2>> $PUB/bench.err | tail -1 > profiles/${TAG}_bench_c2_line.json
+python bench.py --full 2> $PUB/bench.err | tail -1 > profiles/${TAG}_bench_line.json
+python bench.py --full --config c2 2>> $PUB/bench.err | tail -1 > profiles/${TAG}_bench_c2_line.json
 rm -f profiles/${TAG}c2_bench_line.json
-python bench.py --config c4 --no-cpu-baseline 2>> $PUB/bench.err | tail -1 > profiles/${TAG}_bench_c4_1gpu_line.json
-python bench.py --config c5 --no-cpu-baseline --no-decode 2>> $PUB/bench.err | tail -1 > profiles/${TAG}_bench_c5_1gpu_line.json
+python bench.py --full --config c4 --no-cpu-baseline 2>> $PUB/bench.err | tail -1 > profiles/${TAG}_bench_c4_1gpu_line.json
+python bench.py --full --config c5 --no-cpu-baseline --no-decode 2>> $PUB/bench.err | tail -1 > profiles/${TAG}_bench_c5_1gpu_line.json
 tools/emu_lines.sh profiles/${TAG}_emulation.jsonl > $PUB/emu.log 2>&1
 cp profiles/${TAG}_* profiles/${TAG}c2_* $PUB/
 ls -la $PUB | tail -40

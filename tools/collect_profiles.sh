@@ -7,9 +7,9 @@ TAG=$1; shift
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-python bench.py "$@" > $OUT/bench_line.json 2> $OUT/bench.err
+python bench.py --full "$@" > $OUT/bench_line.json 2> $OUT/bench.err
 tail -c 600 $OUT/bench_line.json
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o st -- python bench.py --no-cpu-baseline --no-decode "$@" > $OUT/stats.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o st -- python bench.py --full --no-cpu-baseline --no-decode "$@" > $OUT/stats.log 2>&1
 python tools/kstats.py $(find $OUT/stats -name "*kernel_stats.csv" | head -1) 30 > $OUT/kernel_stats_bench.md
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_dec -o st -- python tools/prof_decode.py > $OUT/stats_dec.log 2>&1
 python tools/kstats.py $(find $OUT/stats_dec -name "*kernel_stats.csv" | head -1) 30 > $OUT/kernel_stats_decode.md

@@ -4,7 +4,7 @@
 OUT=$1; : > $OUT
 for spec in "c3 1" "c3 2" "c3 4" "c3 8" "c4 4" "c5 8"; do
   set -- $spec
-  python bench.py --no-cpu-baseline --no-decode --config $1 --emulate-world $2 2>/dev/null | tail -1 | python -c "
+  python bench.py --full --no-cpu-baseline --no-decode --config $1 --emulate-world $2 2>/dev/null | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 keep={k:d[k] for k in ('metric','value','unit','ms_per_step','stage_ms','config','roofline_chain')}

@@ -36,7 +36,7 @@ for n in fetch:
     short = re.sub(r"<.*", "", n)
     out["kernels"][n[:60]] = f + w
 # average duration of the same kernels INSIDE the two-stream bench step (kernel_stats_bench.md of the same collection: the rocprofv3
-# trace of `python bench.py`, whose launches are overwhelmingly the step's) -- bench.py's roofline.dominant_kernel.ms_per_launch_in_step
+# trace of `python bench.py --full`, whose launches are overwhelmingly the step's) -- bench.py's roofline.dominant_kernel.ms_per_launch_in_step
 import os
 ksb = f"{src}/kernel_stats_bench.md"
 if os.path.exists(ksb):

@@ -10,7 +10,7 @@ sha = open(os.path.join(src, "lib.sha256")).read().split()[0]
 line = open(os.path.join(src, "bench_line.json")).read().strip().splitlines()[-1]
 json.loads(line)
 open(dst + "_bench_line.json", "w").write(line + "\n")
-hdr = {"bench": "`rocprofv3 --kernel-trace --stats -- python bench.py --no-cpu-baseline --no-decode` (default N=1, config c3; the "
+hdr = {"bench": "`rocprofv3 --kernel-trace --stats -- python bench.py --full --no-cpu-baseline --no-decode` (default N=1, config c3; the "
                 "run also contains the warm-up steps, the per-kernel timing passes and the attention-by-batch calls)",
        "decode": "`rocprofv3 --kernel-trace --stats -- python tools/prof_decode.py` (FastGearDecoder, Llama-2-7B shapes, prompt 4040, "
                  "2 % outliers, 20 + 20 timed eager token steps after the prefill; hipBLASLt kernels = the prefill GEMMs)"}

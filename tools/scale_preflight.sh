@@ -23,11 +23,11 @@ for CFG in c3 c4 c5; do
     EXTRA=""
     [ $CFG = c5 ] && EXTRA="--no-decode"      # (70B weights do not fit beside the fused copies on one GPU; the attention legs run)
     if [ $N -eq 1 ]; then
-      python bench.py --gpus 1 --config $CFG --no-cpu-baseline $EXTRA > $LOG.json 2> $LOG.err
+      python bench.py --full --gpus 1 --config $CFG --no-cpu-baseline $EXTRA > $LOG.json 2> $LOG.err
     else
       PORT=$((PORT+1))
       python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port $PORT \
-        bench.py --gpus $N --config $CFG --exchange both --no-cpu-baseline $EXTRA > $LOG.json 2> $LOG.err
+        bench.py --full --gpus $N --config $CFG --exchange both --no-cpu-baseline $EXTRA > $LOG.json 2> $LOG.err
     fi
     python - $LOG.json $CFG $N <<'PY' | tee -a $OUT/summary.txt
 import json, sys
