@@ -296,6 +296,26 @@ def _compress_into(bufs, d, lead, B, H, D, k_src, v_src, T, t_off, seg, kk, o_of
         L.check(rc, "gear_cache_tiles_build")
 
 
+N_MAX_EXTEND = 2048      # query tokens per gear_attn_extend_cache call
+
+
+def _check_rows(k, v, B, H, D, n):
+    want = (B, H, n, D)
+    if tuple(k.shape) != want or tuple(v.shape) != want or k.dtype != torch.float16 or v.dtype != torch.float16:
+        raise ValueError(f"extend: K / V must be fp16 {list(want)}, got {list(k.shape)} {k.dtype} / {list(v.shape)} {v.dtype}")
+
+
+def _check_room(c, n):
+    """Refuse (before anything changes) n tokens that would take the compressed part past its capacity."""
+    if n < 1:
+        raise ValueError(f"extend: n = {n}, at least one token")
+    fill = c.n_win + n
+    n_comp = c.n_comp + (fill // c.R) * c.R
+    if n_comp > c.Tmax:
+        raise L.GearError(f"extend: {n} tokens after {c.seq_len} would compress {n_comp} tokens, the cache holds {c.Tmax}: "
+                          "capacity exceeded")
+
+
 class GearKVCachePool:
     """The buffers of ALL layers' caches as one tensor per field with a leading layer dimension.  Every layer's
     GearKVCache takes its (contiguous) slice, so nothing changes for the kernels; what the pool buys is the block boundary:
@@ -347,6 +367,32 @@ class GearKVCachePool:
             c.n_comp += R
             c.n_win = 0
 
+    def extend_all(self, k_list, v_list) -> int:
+        """Commit n new tokens to every layer: k_list / v_list hold one fp16 [B, H, n, 128] (post-RoPE) per layer.  The windows
+        fill up to `residual` and compress_all() runs at each boundary, exactly as n token steps would run it (same window
+        contents, same generator order), so the result is bit-identical to that.  Refused before anything changes when the
+        cache cannot take the tokens.  Returns the number of block boundaries crossed."""
+        c0, R = self.caches[0], self.dims["R"]
+        if len(k_list) != self.L or len(v_list) != self.L:
+            raise ValueError(f"extend_all: {len(k_list)} / {len(v_list)} K / V tensors for {self.L} layers")
+        n = k_list[0].shape[2]
+        for k, v in zip(k_list, v_list):
+            _check_rows(k, v, self.B, self.H, self.D, n)
+        _check_room(c0, n)
+        done = nb = 0
+        while done < n:
+            m = min(R - c0.n_win, n - done)
+            w = c0.n_win
+            for c, k, v in zip(self.caches, k_list, v_list):
+                c.kwin[:, :, w:w + m] = k[:, :, done:done + m]
+                c.vwin[:, :, w:w + m] = v[:, :, done:done + m]
+                c.n_win += m
+            done += m
+            if c0.n_win == R:
+                self.compress_all()
+                nb += 1
+        return nb
+
 
 class GearKVCache:
     def __init__(self, batch: int, n_kv_heads: int, max_tokens: int, compress_config: dict, device, head_dim: int = 128,
@@ -386,6 +432,7 @@ class GearKVCache:
         self.gen = torch.Generator(device=device)
         self.gen.manual_seed(seed)
         self._ws = None
+        self._xws = None
         self.use_tiles = True     # tests switch these off to compare the list paths
         self.use_chunk_index = True
         self._views = {}
@@ -480,6 +527,45 @@ class GearKVCache:
             self._store(self.kwin, self.vwin, self.R, seg, self.kk_blk, o_off)
             self.n_win = 0
 
+    def attend_extend(self, q: torch.Tensor, k_new: torch.Tensor, v_new: torch.Tensor) -> torch.Tensor:
+        """Chunk attention: q fp16 [B,Hq,n,128] at positions seq_len .. seq_len + n - 1, k_new / v_new fp16 [B,Hkv,n,128] (post-RoPE)
+        -> fp16 [B,Hq,n,128].  Query i attends over the compressed tokens, the window and chunk rows 0 .. i (one fp32 softmax,
+        gear_attn_extend_cache).  Changes no state; extend() commits the rows.  At most N_MAX_EXTEND tokens per call."""
+        B, Hq, n = q.shape[0], q.shape[1], q.shape[2]
+        _check_rows(k_new, v_new, self.B, self.H, self.D, n)
+        if tuple(q.shape) != (self.B, Hq, n, self.D) or q.dtype != torch.float16:
+            raise ValueError(f"attend_extend: q must be fp16 [{self.B}, Hq, {n}, {self.D}], got {list(q.shape)} {q.dtype}")
+        lib = L.load()
+        q, k_new, v_new = q.contiguous(), k_new.contiguous(), v_new.contiguous()
+        out = torch.empty_like(q)
+        wsb = lib.gear_attn_extend_workspace(B, Hq, n, self.n_comp, self.n_win)
+        if self._xws is None or self._xws.numel() < wsb:
+            self._xws = torch.empty((wsb,), dtype=torch.uint8, device=q.device)
+        key = (self.kk0, self.seg0, True, True, True)
+        view = self._views.get(key)
+        if view is None:
+            view = self._views[key] = _view(self.bufs, self.dims, B, self.H, self.D, self.kk0, self.seg0, kwin=True)
+        rc = lib.gear_attn_extend_cache(C_.byref(view), L.ptr(q), Hq, n, self.n_comp, self.n_win, L.ptr(k_new), L.ptr(v_new),
+                                        1.0 / math.sqrt(self.D), L.ptr(out), None, L.ptr(self._xws), self._xws.numel(),
+                                        L.stream_ptr(q))
+        L.check(rc, "gear_attn_extend_cache")
+        return out
+
+    def extend(self, k_new: torch.Tensor, v_new: torch.Tensor):
+        """Commit n tokens (fp16 [B,Hkv,n,128], post-RoPE): through the window, compressing each time it holds `residual` tokens --
+        bit-identical to n x (append + maybe_compress).  Refused before anything changes when the cache cannot take them."""
+        n = k_new.shape[2]
+        _check_rows(k_new, v_new, self.B, self.H, self.D, n)
+        _check_room(self, n)
+        done = 0
+        while done < n:
+            m = min(self.R - self.n_win, n - done)
+            self.kwin[:, :, self.n_win:self.n_win + m] = k_new[:, :, done:done + m]
+            self.vwin[:, :, self.n_win:self.n_win + m] = v_new[:, :, done:done + m]
+            self.n_win += m
+            done += m
+            self.maybe_compress()
+
 
 class Fp16KVCache:
     """The UNCOMPRESSED baseline behind the same decoder (the model "None" the reference's harness times beside gearl / KIVI,
@@ -525,4 +611,25 @@ class Fp16KVCache:
     def attend(self, q: torch.Tensor) -> torch.Tensor:
         from .attention import decode_attention_f16
         return decode_attention_f16(q, self.kwin, self.vwin, T=self.n_win)
+
+    def attend_extend(self, q: torch.Tensor, k_new: torch.Tensor, v_new: torch.Tensor) -> torch.Tensor:
+        """Chunk attention of the uncompressed baseline: query i over the cached rows and chunk rows 0 .. i (torch SDPA with the
+        causal offset; not a product path).  Changes no state."""
+        n, Hq = q.shape[2], q.shape[1]
+        _check_rows(k_new, v_new, self.B, self.H, self.D, n)
+        k = torch.cat([self.kwin[:, :, :self.n_win], k_new], 2)
+        v = torch.cat([self.vwin[:, :, :self.n_win], v_new], 2)
+        if Hq != self.H:
+            k, v = k.repeat_interleave(Hq // self.H, 1), v.repeat_interleave(Hq // self.H, 1)
+        mask = torch.ones((n, self.n_win + n), dtype=torch.bool, device=q.device).tril(self.n_win)
+        return torch.nn.functional.scaled_dot_product_attention(q, k, v, attn_mask=mask)
+
+    def extend(self, k_new: torch.Tensor, v_new: torch.Tensor):
+        n = k_new.shape[2]
+        _check_rows(k_new, v_new, self.B, self.H, self.D, n)
+        if self.n_win + n > self.R:
+            raise L.GearError(f"Fp16KVCache: {n} tokens after {self.n_win} exceed the capacity {self.R}")
+        self.kwin[:, :, self.n_win:self.n_win + n] = k_new
+        self.vwin[:, :, self.n_win:self.n_win + n] = v_new
+        self.n_win += n
 

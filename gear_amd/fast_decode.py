@@ -223,6 +223,65 @@ class FastGearDecoder:
         self._state_dirty = True
         return self.model.lm_head(m.norm(h[:, -1]))
 
+    # ------------------------------------------------------------------------------------------------ chunk extend
+    @torch.no_grad()
+    def extend(self, input_ids: torch.Tensor) -> torch.Tensor:
+        """Feed n tokens [B, n] at once after prefill(): per layer the prefill-style dense projections, RoPE at pos .. pos + n - 1,
+        chunk attention over the layer's cache (compressed part + window + the chunk itself, causal: cache.attend_extend), o_proj
+        and MLP; then the tokens are committed (the windows fill, every `residual` tokens the pooled block compressor runs, exactly
+        as n step() calls would run it).  Returns the logits of every position [B, n, vocab].
+        More than N_MAX_EXTEND (2048) tokens go in pieces of that size, each committed before the next: a later piece sees the
+        earlier ones as ordinary cache contents (compressed where a block boundary was crossed).  A call that would exceed the cache
+        capacity is refused before anything changes."""
+        from .cache import N_MAX_EXTEND, _check_room
+        if self.tp_world > 1:
+            raise NotImplementedError("extend(): head-sharded (tp_world > 1) chunk extend is not implemented -- use step()")
+        if torch.cuda.is_current_stream_capturing():
+            raise NotImplementedError("extend(): chunk extend cannot be captured in a graph (host-side counters, block boundaries)")
+        if self.pos == 0:
+            raise ValueError("extend(): run prefill() first")
+        if input_ids.dim() != 2 or input_ids.shape[0] != self.batch or input_ids.shape[1] < 1:
+            raise ValueError(f"extend(): input_ids must be [{self.batch}, n >= 1], got {list(input_ids.shape)}")
+        n = input_ids.shape[1]
+        c0 = self.layers[0]["cache"]
+        if self.pool is not None:
+            _check_room(c0, n)
+        elif c0.n_win + n > c0.R:
+            raise L.GearError(f"extend(): {n} tokens after {c0.n_win} exceed the fp16 cache's capacity {c0.R}")
+        out = [self._extend_piece(input_ids[:, i:i + N_MAX_EXTEND]) for i in range(0, n, N_MAX_EXTEND)]
+        return out[0] if len(out) == 1 else torch.cat(out, 1)
+
+    def _extend_piece(self, ids):
+        B, n = ids.shape
+        m = self.model.model
+        h = m.embed_tokens(ids)
+        pos = torch.arange(self.pos, self.pos + n, device=self.dev).unsqueeze(0)
+        Hq, Hkv, D = self.Hq, self.Hkv, self.D
+        ks, vs = [], []
+        for lw, layer in zip(self.layers, m.layers):
+            qkv = F.linear(self._unit_rms(h), lw["wqkv"])       # input_layernorm's weight lives in wqkv's columns
+            q, k, v = qkv.split([Hq * D, Hkv * D, Hkv * D], dim=-1)
+            q = q.view(B, n, Hq, D).transpose(1, 2)
+            k = k.view(B, n, Hkv, D).transpose(1, 2)
+            v = v.view(B, n, Hkv, D).transpose(1, 2).contiguous()
+            cos, sin = lw["rotary"](v, pos)
+            q, k = apply_rotary_pos_emb(q, k, cos, sin)
+            q, k = q.contiguous(), k.contiguous()
+            a = lw["cache"].attend_extend(q, k, v)
+            ks.append(k)
+            vs.append(v)
+            h = h + F.linear(a.transpose(1, 2).reshape(B, n, Hq * D), lw["wo"])
+            h = h + layer.mlp(layer.post_attention_layernorm(h))
+        if self.pool is not None:
+            for _ in range(self.pool.extend_all(ks, vs)):
+                self._after_boundary()
+        else:
+            for lw, k, v in zip(self.layers, ks, vs):
+                lw["cache"].extend(k, v)
+        self.pos += n
+        self._state_dirty = True          # a later step_graph() brings the device-side state up to date
+        return self.model.lm_head(m.norm(h))
+
     # ------------------------------------------------------------------------------------------------ decode
     @torch.no_grad()
     def step(self, token_ids: torch.Tensor) -> torch.Tensor:

@@ -385,6 +385,20 @@ typedef struct gear_cache_view {
  * dependent loads), else through the chunk indices, else by binary search in the lists. */
 int gear_attn_decode_cache(const gear_cache_view* c, const void* q, int Hq, int T, int W, const void* dyn_state, float qscale,
                            void* out, void* lse, void* workspace, size_t workspace_bytes, void* stream);
+/* ---- chunk attention: extend a cache by n tokens at once -----------------------------------------------------------------
+ * Replaces n single-token decode steps (n x gear_attn_decode_cache, each reading the whole compressed prefix) when a block of
+ * tokens enters a cache that already holds T compressed + W window tokens (second chat turn, speculative verification, a prompt
+ * that arrives in parts).  Query i (0 <= i < n) attends with one fp32 softmax over the T compressed tokens (reconstructed as
+ * gear_attn_decode_cache does: dequant, stored outlier values in place of the dequantized ones, + Q P^T of the token's factor
+ * segment), the W window tokens and the chunk's own rows 0 .. i (causal).  Changes no cache state.
+ *   c      the cache view (mode 0, bits 2 / 4, group 32 / 64, rank <= 16, T % 64 == 0, W <= wcap; outliers from the lists)
+ *   q      fp16 [B, Hq, n, 128]; k_new / v_new fp16 [B, Hkv, n, 128] (post-RoPE), 1 <= n <= 2048, Hq % Hkv == 0
+ *   out    fp16 [B, Hq, n, 128]; lse optional float [B, Hq, n] (log-sum-exp of the scaled scores)
+ *   workspace: gear_attn_extend_workspace(B, Hq, n, T, W) bytes (bounds every Hkv that divides Hq).  Two launches. */
+size_t gear_attn_extend_workspace(int B, int Hq, int n, int T, int W);
+int gear_attn_extend_cache(const gear_cache_view* c, const void* q, int Hq, int n, int T, int W, const void* k_new,
+                           const void* v_new, float qscale, void* out, void* lse, void* workspace, size_t workspace_bytes,
+                           void* stream);
 /* (Re)build the sparse tiles of K chunks [k_chunk0, k_chunk1) (128 tokens each) and V blocks [v_blk0, v_blk1) (64 tokens each) of a
  * cache that holds T compressed tokens: called after the prompt and after every appended block (the chunk the block lies in). */
 int gear_cache_tiles_build(const gear_cache_view* c, int T, int k_chunk0, int k_chunk1, int v_blk0, int v_blk1, void* stream);
