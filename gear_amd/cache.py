@@ -483,10 +483,11 @@ class GearKVCache:
         self.vwin[:, :, self.n_win] = v_new[:, :, 0]
         self.n_win += 1
 
-    def _attend(self, q, T, W, dyn):
+    def _attend(self, q, T, W, dyn, return_lse=False):
         B, Hq = q.shape[0], q.shape[1]
         lib = L.load()
         out = torch.empty((B, Hq, 1, self.D), dtype=torch.float16, device=q.device)
+        lse = torch.empty((B, Hq), dtype=torch.float32, device=q.device) if return_lse else None
         wsb = lib.gear_attn_decode_workspace(B, Hq, self.Tmax, self.bits)
         if self._ws is None or self._ws.numel() < wsb:
             self._ws = torch.empty((wsb,), dtype=torch.uint8, device=q.device)
@@ -499,14 +500,16 @@ class GearKVCache:
             if not self.use_chunk_index:
                 view.kochunk = view.vochunk = None
             self._views[key] = view
-        rc = lib.gear_attn_decode_cache(C_.byref(view), L.ptr(q), Hq, T, W, L.ptr(dyn), 1.0 / math.sqrt(self.D), L.ptr(out), None,
-                                        L.ptr(self._ws), self._ws.numel(), L.stream_ptr(q))
+        rc = lib.gear_attn_decode_cache(C_.byref(view), L.ptr(q), Hq, T, W, L.ptr(dyn), 1.0 / math.sqrt(self.D), L.ptr(out),
+                                        L.ptr(lse), L.ptr(self._ws), self._ws.numel(), L.stream_ptr(q))
         L.check(rc, "gear_attn_decode_cache")
-        return out
+        return (out, lse) if return_lse else out
 
-    def attend(self, q: torch.Tensor) -> torch.Tensor:
-        """q fp16 [B,Hq,1,128] -> softmax(q Khat^T / sqrt(128)) Vhat over compressed + window tokens, fp16 [B,Hq,1,128]."""
-        return self._attend(q, self.n_comp, self.n_win, None)
+    def attend(self, q: torch.Tensor, return_lse: bool = False):
+        """q fp16 [B,Hq,1,128] -> softmax(q Khat^T / sqrt(128)) Vhat over compressed + window tokens, fp16 [B,Hq,1,128]; with
+        return_lse also the fp32 [B,Hq] log-sum-exp of the scaled scores (the merge then runs in its own launch: attn_fold
+        does not apply)."""
+        return self._attend(q, self.n_comp, self.n_win, None, return_lse)
 
     # ---- device-state variants: no host-side counters change here (a captured graph replays these launches) ----------
     def append_rope_dyn(self, qkv: torch.Tensor, n_q_heads: int, theta: float) -> torch.Tensor:
@@ -527,10 +530,11 @@ class GearKVCache:
             self._store(self.kwin, self.vwin, self.R, seg, self.kk_blk, o_off)
             self.n_win = 0
 
-    def attend_extend(self, q: torch.Tensor, k_new: torch.Tensor, v_new: torch.Tensor) -> torch.Tensor:
+    def attend_extend(self, q: torch.Tensor, k_new: torch.Tensor, v_new: torch.Tensor, return_lse: bool = False):
         """Chunk attention: q fp16 [B,Hq,n,128] at positions seq_len .. seq_len + n - 1, k_new / v_new fp16 [B,Hkv,n,128] (post-RoPE)
-        -> fp16 [B,Hq,n,128].  Query i attends over the compressed tokens, the window and chunk rows 0 .. i (one fp32 softmax,
-        gear_attn_extend_cache).  Changes no state; extend() commits the rows.  At most N_MAX_EXTEND tokens per call."""
+        -> fp16 [B,Hq,n,128] (with return_lse also the fp32 [B,Hq,n] log-sum-exp of the scaled scores).  Query i attends over the
+        compressed tokens, the window and chunk rows 0 .. i (one fp32 softmax, gear_attn_extend_cache).  Changes no state; extend()
+        commits the rows.  At most N_MAX_EXTEND tokens per call."""
         B, Hq, n = q.shape[0], q.shape[1], q.shape[2]
         _check_rows(k_new, v_new, self.B, self.H, self.D, n)
         if tuple(q.shape) != (self.B, Hq, n, self.D) or q.dtype != torch.float16:
@@ -538,6 +542,7 @@ class GearKVCache:
         lib = L.load()
         q, k_new, v_new = q.contiguous(), k_new.contiguous(), v_new.contiguous()
         out = torch.empty_like(q)
+        lse = torch.empty((B, Hq, n), dtype=torch.float32, device=q.device) if return_lse else None
         wsb = lib.gear_attn_extend_workspace(B, Hq, n, self.n_comp, self.n_win)
         if self._xws is None or self._xws.numel() < wsb:
             self._xws = torch.empty((wsb,), dtype=torch.uint8, device=q.device)
@@ -546,10 +551,10 @@ class GearKVCache:
         if view is None:
             view = self._views[key] = _view(self.bufs, self.dims, B, self.H, self.D, self.kk0, self.seg0, kwin=True)
         rc = lib.gear_attn_extend_cache(C_.byref(view), L.ptr(q), Hq, n, self.n_comp, self.n_win, L.ptr(k_new), L.ptr(v_new),
-                                        1.0 / math.sqrt(self.D), L.ptr(out), None, L.ptr(self._xws), self._xws.numel(),
+                                        1.0 / math.sqrt(self.D), L.ptr(out), L.ptr(lse), L.ptr(self._xws), self._xws.numel(),
                                         L.stream_ptr(q))
         L.check(rc, "gear_attn_extend_cache")
-        return out
+        return (out, lse) if return_lse else out
 
     def extend(self, k_new: torch.Tensor, v_new: torch.Tensor):
         """Commit n tokens (fp16 [B,Hkv,n,128], post-RoPE): through the window, compressing each time it holds `residual` tokens --

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 import torch
 
+import attn_probe as AP
 from conftest import rel_fro
 from oracle import oracle as orc
 
@@ -17,40 +18,9 @@ def host(t):
 
 
 def _reconstruct_cache(c):
-    """float64 [B,H,n_comp,128] K and V from the cache buffers (dequant + per-segment Q P^T)."""
-    n, g, b = c.n_comp, c.group, c.bits
-    fpi = 32 // b
-    kq = orc.unpack_tensor(host(c.kcode[:, :, :, :n // fpi]), b, 3).astype(np.float64)                # [B,H,D,n]
-    K = (kq * np.repeat(host(c.kscale[:, :, :, :n // g]).astype(np.float64), g, 3)
-         + np.repeat(host(c.kmn[:, :, :, :n // g]).astype(np.float64), g, 3)).transpose(0, 1, 3, 2)
-    vq = orc.unpack_tensor(host(c.vcode[:, :, :n]), b, 3).astype(np.float64)                           # [B,H,n,D]
-    V = vq * np.repeat(host(c.vscale[:, :, :n]).astype(np.float64), g, 3) + np.repeat(host(c.vmn[:, :, :n]).astype(np.float64), g, 3)
-    # sparse part: a stored outlier replaces the DEQUANTIZED value at its position; the low-rank term is added on top, as in the
-    # simulated path (output + error_lr with the outliers restored in output, compress_function.py:204-220)
-    if c.kk_blk and n:
-        klen = c.kk0 + ((n - c.seg0) // c.R) * c.kk_blk
-        oi = host(c.koidx[..., :klen]).astype(np.int64) & 0xFFFF                       # [B,H,D,2,klen] token indices
-        ov = host(c.koval[..., :klen]).astype(np.float64)
-        B_, H_, D_ = oi.shape[:3]
-        for b_ in range(B_):
-            for h_ in range(H_):
-                for d_ in range(D_):
-                    K[b_, h_, oi[b_, h_, d_].reshape(-1), d_] = ov[b_, h_, d_].reshape(-1)
-    if c.kv and n:
-        oi = host(c.voidx[:, :n]).astype(np.int64) & 0xFFFF                            # [B,n,2kv] column h*128 + d
-        ov = host(c.voval[:, :n]).astype(np.float64)
-        for b_ in range(oi.shape[0]):
-            for t_ in range(n):
-                V[b_, oi[b_, t_] // 128, t_, oi[b_, t_] % 128] = ov[b_, t_]
-    if c.lowrank:
-        t = 0
-        while t < n:
-            seg = c._segment_of(t)
-            te = c.seg0 if seg == 0 else min(n, t + c.R)
-            K[:, :, t:te] += host(c.kQtok[:, :, t:te]).astype(np.float64) @ host(c.kPseg[seg]).astype(np.float64).transpose(0, 1, 3, 2)
-            V[:, :, t:te] += host(c.vQtok[:, :, t:te]).astype(np.float64) @ host(c.vPseg[seg]).astype(np.float64).transpose(0, 1, 3, 2)
-            t = te
-    return K, V
+    """float64 [B,H,n_comp,128] K and V from the cache buffers (dequant + per-segment Q P^T; a stored outlier replaces the
+    dequantized value, the low-rank term on top) -- attn_probe's."""
+    return AP.reconstruct_cache(c)
 
 
 def _ref_attn(q, K, V, kw, vw, n_rep):

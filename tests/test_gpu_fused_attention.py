@@ -6,8 +6,8 @@ import numpy as np
 import pytest
 import torch
 
+import attn_probe as AP
 from conftest import rel_fro
-from oracle import oracle as orc
 
 pytestmark = pytest.mark.gpu
 
@@ -17,34 +17,8 @@ def host(t):
 
 
 def reconstruct(p):
-    """Payload -> float64 [B,H,T,D]: dequant + Q P^T, outlier entries = value + Q P^T (no fp16 rounding)."""
-    B, H, T, D = p.shape
-    code, scale, mn = host(p.code), host(p.scale).astype(np.float64), host(p.mn).astype(np.float64)
-    if p.kind == "v":
-        q = orc.unpack_tensor(code, p.bits, 3).astype(np.float64)                       # [B,H,T,D]
-        deq = q * np.repeat(scale, p.group, axis=3) + np.repeat(mn, p.group, axis=3)
-    else:
-        q = orc.unpack_tensor(code, p.bits, 3).astype(np.float64)                       # [B,H,D,T]
-        deq = (q * np.repeat(scale, p.group, axis=3) + np.repeat(mn, p.group, axis=3)).transpose(0, 1, 3, 2)
-    lr = 0.0
-    if p.P is not None:
-        lr = host(p.Q).astype(np.float64) @ host(p.P).astype(np.float64).transpose(0, 1, 3, 2)
-    rec = deq + lr
-    if p.oidx is not None:
-        oi, ov = host(p.oidx).astype(np.int64), host(p.oval).astype(np.float64)
-        if p.kind == "v":      # rows (b,t) over columns h*D+d
-            for b in range(B):
-                for t in range(T):
-                    h, d = oi[b, t] // D, oi[b, t] % D
-                    base = ov[b, t]
-                    rec[b, h, t, d] = base + (lr[b, h, t, d] if p.P is not None else 0.0)
-        else:                  # rows (b,h,d) over tokens
-            for b in range(B):
-                for h in range(H):
-                    for d in range(D):
-                        t = oi[b, h, d]
-                        rec[b, h, t, d] = ov[b, h, d] + (lr[b, h, t, d] if p.P is not None else 0.0)
-    return rec
+    """Payload -> float64 [B,H,T,D]: dequant + Q P^T, outlier entries = value + Q P^T (no fp16 rounding) -- attn_probe's."""
+    return AP.reconstruct_payload(p)
 
 
 def ref_attention(q, khat, vhat, kwin, vwin, n_rep):
