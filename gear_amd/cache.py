@@ -297,6 +297,7 @@ def _compress_into(bufs, d, lead, B, H, D, k_src, v_src, T, t_off, seg, kk, o_of
 
 
 N_MAX_EXTEND = 2048      # query tokens per gear_attn_extend_cache call
+N_MAX_VERIFY = 16        # query tokens per gear_attn_verify_cache call
 
 
 def _check_rows(k, v, B, H, D, n):
@@ -433,6 +434,7 @@ class GearKVCache:
         self.gen.manual_seed(seed)
         self._ws = None
         self._xws = None
+        self._vws = None
         self.use_tiles = True     # tests switch these off to compare the list paths
         self.use_chunk_index = True
         self._views = {}
@@ -556,6 +558,37 @@ class GearKVCache:
         L.check(rc, "gear_attn_extend_cache")
         return (out, lse) if return_lse else out
 
+    def attend_verify(self, q: torch.Tensor, k_new: torch.Tensor, v_new: torch.Tensor, return_lse: bool = False):
+        """attend_extend for the draft sizes of speculative decoding (n <= N_MAX_VERIFY): the same result through the decode
+        kernels (gear_attn_verify_cache; the attention options apply as for attend(), except attn_fold).  Changes no state."""
+        B, Hq, n = q.shape[0], q.shape[1], q.shape[2]
+        if n > N_MAX_VERIFY:
+            raise ValueError(f"attend_verify: n = {n} query tokens, at most N_MAX_VERIFY = {N_MAX_VERIFY}: use attend_extend")
+        _check_rows(k_new, v_new, self.B, self.H, self.D, n)
+        if tuple(q.shape) != (self.B, Hq, n, self.D) or q.dtype != torch.float16:
+            raise ValueError(f"attend_verify: q must be fp16 [{self.B}, Hq, {n}, {self.D}], got {list(q.shape)} {q.dtype}")
+        lib = L.load()
+        q, k_new, v_new = q.contiguous(), k_new.contiguous(), v_new.contiguous()
+        out = torch.empty_like(q)
+        lse = torch.empty((B, Hq, n), dtype=torch.float32, device=q.device) if return_lse else None
+        wsb = lib.gear_attn_verify_workspace(B, Hq, n, self.n_comp, self.n_win)
+        if self._vws is None or self._vws.numel() < wsb:
+            self._vws = torch.empty((wsb,), dtype=torch.uint8, device=q.device)
+        key = (self.kk0, self.seg0, True, self.use_tiles, self.use_chunk_index)
+        view = self._views.get(key)
+        if view is None:
+            view = _view(self.bufs, self.dims, B, self.H, self.D, self.kk0, self.seg0, kwin=True)
+            if not self.use_tiles:
+                view.ktile = view.vtile = None
+            if not self.use_chunk_index:
+                view.kochunk = view.vochunk = None
+            self._views[key] = view
+        rc = lib.gear_attn_verify_cache(C_.byref(view), L.ptr(q), Hq, n, self.n_comp, self.n_win, L.ptr(k_new), L.ptr(v_new),
+                                        1.0 / math.sqrt(self.D), L.ptr(out), L.ptr(lse), L.ptr(self._vws), self._vws.numel(),
+                                        L.stream_ptr(q))
+        L.check(rc, "gear_attn_verify_cache")
+        return (out, lse) if return_lse else out
+
     def extend(self, k_new: torch.Tensor, v_new: torch.Tensor):
         """Commit n tokens (fp16 [B,Hkv,n,128], post-RoPE): through the window, compressing each time it holds `residual` tokens --
         bit-identical to n x (append + maybe_compress).  Refused before anything changes when the cache cannot take them."""
@@ -628,6 +661,22 @@ class Fp16KVCache:
             k, v = k.repeat_interleave(Hq // self.H, 1), v.repeat_interleave(Hq // self.H, 1)
         mask = torch.ones((n, self.n_win + n), dtype=torch.bool, device=q.device).tril(self.n_win)
         return torch.nn.functional.scaled_dot_product_attention(q, k, v, attn_mask=mask)
+
+    def attend_verify(self, q: torch.Tensor, k_new: torch.Tensor, v_new: torch.Tensor, return_lse: bool = False):
+        """The speculative-verify interface of GearKVCache on the baseline: attend_extend (torch SDPA), with return_lse also the
+        fp32 [B, Hq, n] log-sum-exp of the scaled scores.  Changes no state."""
+        n, Hq = q.shape[2], q.shape[1]
+        if n > N_MAX_VERIFY:
+            raise ValueError(f"attend_verify: n = {n} query tokens, at most N_MAX_VERIFY = {N_MAX_VERIFY}: use attend_extend")
+        out = self.attend_extend(q, k_new, v_new)
+        if not return_lse:
+            return out
+        k = torch.cat([self.kwin[:, :, :self.n_win], k_new], 2).float()
+        if Hq != self.H:
+            k = k.repeat_interleave(Hq // self.H, 1)
+        s = torch.einsum("bhid,bhtd->bhit", q.float(), k) / math.sqrt(self.D)
+        mask = torch.ones((n, self.n_win + n), dtype=torch.bool, device=q.device).tril(self.n_win)
+        return out, torch.logsumexp(s.masked_fill(~mask, float("-inf")), -1)
 
     def extend(self, k_new: torch.Tensor, v_new: torch.Tensor):
         n = k_new.shape[2]

@@ -1826,7 +1826,9 @@ int attn_decode_impl(const void* q, const void* kcode, const void* kscale, const
                                 int W, int ldk, int lsk, int tcap_v, int tf_k, int tf_v, int group, int bits, int mode,
                                 int rk, int rv, int kk, int kv, int seg0, int seglen, int wcap, const void* dyn_state,
                                 float qscale, void* out, void* lse, void* workspace, size_t workspace_bytes, void* stream,
-                     const void* kochunk, const void* vochunk, const StreamExtras* ex = nullptr) {
+                     const void* kochunk, const void* vochunk, const StreamExtras* ex = nullptr, AttnArgs* keep = nullptr) {
+    // keep != nullptr (gear_attn_verify_cache): launch the partial kernel only -- no fold, no reduce -- and hand the launch's
+    // arguments (slot layout, where the window went) back to the caller, which merges the partials itself
     const int kk_stride = ex ? ex->kk_stride : 0, kk0 = ex ? ex->kk0 : 0, kkb = ex ? ex->kkb : 0, nbk_pitch = ex ? ex->nbk_pitch : 0;
     GEAR_CHECK_ARG(wcap >= W, "gear_attn_decode: window pitch %d smaller than the window %d", wcap, W);
     GEAR_CHECK_ARG(seglen == 0 || (seglen % 64 == 0 && seg0 % 64 == 0 && seg0 >= 0),
@@ -1936,7 +1938,7 @@ int attn_decode_impl(const void* q, const void* kcode, const void* kscale, const
         const bool mf = mf_shape && a.pslots == a.splits;
         // the merge inside the partial launch: vector short-chunk kernel with one query head per workgroup, nothing left for the
         // reduce kernel but the merge (the window is a chunk of the split, or there is none), no log-sum-exp output wanted
-        fold_possible = small && !mf && nrep_t == 1 && !lse && (win_chunk || (W == 0 && !dyn_state)) && a.pslots <= RS_MAX_F &&
+        fold_possible = !keep && small && !mf && nrep_t == 1 && !lse && (win_chunk || (W == 0 && !dyn_state)) && a.pslots <= RS_MAX_F &&
                         fold_wanted((int64_t)B * Hq * a.pslots);
         if (fold_possible && (a.arrive = fold_counters()) != nullptr) a.fold = 1;
         const dim3 gridm((unsigned)(nrep_m > 1 ? Hkv : Hq), a.pslots, (unsigned)B);
@@ -1964,6 +1966,7 @@ int attn_decode_impl(const void* q, const void* kcode, const void* kscale, const
 #undef GOM
         GEAR_CHECK_LAUNCH("gear_attn_decode(partial)");
     }
+    if (keep) { *keep = a; return 0; }
     if (a.fold) return 0;                                  // (the last workgroup of every query head has merged)
     hipLaunchKernelGGL(attn_decode_reduce_kernel, dim3((unsigned)(B * Hq)), dim3(512), 0, st, a, (const uint16_t*)kwin,
                        (const uint16_t*)vwin, W, wcap, (uint16_t*)out, (float*)lse);
@@ -2257,4 +2260,172 @@ extern "C" int gear_attn_decode_cache(const gear_cache_view* c, const void* q, i
                             c->vQ, c->voidx, c->voval, c->kwin, c->vwin, c->B, Hq, c->Hkv, c->D, T, W, c->ldk, c->lsk, c->tcap,
                             c->tcap, c->tcap, c->group, c->bits, c->mode, c->rk, c->rv, kk, c->kv, c->seg0, c->seglen, c->wcap,
                             dyn_state, qscale, out, lse, workspace, workspace_bytes, stream, c->kochunk, c->vochunk, &ex);
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// Speculative verify: n <= 16 query tokens at once over the cache (see include/gear_hip.h).  The decode kernels map a query head to
+// its KV head only through hq / (Hq / Hkv), so q [B, Hq, n, 128] goes to the decode partial dispatch as [B, Hq n, 128]: G n query rows
+// per KV head, every row's compressed-part (and, where the plan puts it there, window) partials computed by the unchanged kernels --
+// the matrix-core kernel reads and reconstructs each compressed chunk once for all of them when G n is 2, 4 or 8.  The merge below
+// then adds what only differs between the rows: chunk rows 0 .. i of the draft (causal).
+namespace {
+
+constexpr int VN_MAX = 16;              // query tokens per verify call
+constexpr int VK_MAX = 128 + VN_MAX;    // keys the merge scores itself: window rows (<= 128) + chunk rows
+
+struct VerifyMerge {
+    const uint16_t* q;                  // [B Hq n, 128]
+    const float* part_o;                // the partial dispatch's slots (rows = B Hq n)
+    const float* part_ml;
+    int pslots, ns;                     // slot pitch, slots to merge (0: no compressed part)
+    const uint16_t* kwin;               // [B Hkv, wcap, 128]
+    const uint16_t* vwin;
+    int Wm, wcap;                       // window rows scored here (0 when they rode along as a slot)
+    const uint16_t* knew;               // [B Hkv, n, 128]
+    const uint16_t* vnew;
+    int Hq, Hkv, n;
+    float qscale;
+    uint16_t* out;                      // [B Hq n, 128]
+    float* lse;                         // [B Hq n] or null
+};
+
+// one output row x = (b, hq, i) per workgroup: scores of the Wm window rows and chunk rows 0 .. i (8 threads per key, 16 channels
+// each), one fp32 softmax with the slots' (m, l), then the weighted sum (two groups of 128 channel threads)
+__global__ __launch_bounds__(256) void attn_verify_merge_kernel(VerifyMerge v) {
+    __shared__ float qs[AD];
+    __shared__ float sc[VK_MAX];
+    __shared__ float sml[2][RS_MAX];
+    __shared__ float coef[RS_MAX + VK_MAX];
+    __shared__ float og[2][AD];
+    __shared__ float stat[2];
+    const int tid = threadIdx.x;
+    const int64_t x = blockIdx.x;
+    const int i = (int)(x % v.n);
+    const int64_t bhq = x / v.n;
+    const int b = (int)(bhq / v.Hq), hq = (int)(bhq % v.Hq);
+    const int64_t bhk = (int64_t)b * v.Hkv + hq / (v.Hq / v.Hkv);
+    const int nk = v.Wm + i + 1;
+    if (tid < AD) qs[tid] = h2f_bits(v.q[x * AD + tid]) * v.qscale;
+    if (tid < v.ns) {
+        sml[0][tid] = v.part_ml[(x * v.pslots + tid) * 2];
+        sml[1][tid] = v.part_ml[(x * v.pslots + tid) * 2 + 1];
+    }
+    __syncthreads();
+    const int kj = tid >> 3, part = tid & 7;
+    for (int k0 = 0; k0 < nk; k0 += 32) {                  // (block-uniform)
+        const int k = k0 + kj;
+        float acc = 0.0f;
+        if (k < nk) {
+            const uint16_t* kr = k < v.Wm ? v.kwin + (bhk * v.wcap + k) * (int64_t)AD : v.knew + (bhk * v.n + k - v.Wm) * (int64_t)AD;
+            const uint4* kr4 = (const uint4*)(kr + part * 16);
+            float t[8];
+            unpack8(kr4[0], t);
+#pragma unroll
+            for (int c = 0; c < 8; c++) acc = fmaf(qs[part * 16 + c], t[c], acc);
+            unpack8(kr4[1], t);
+#pragma unroll
+            for (int c = 0; c < 8; c++) acc = fmaf(qs[part * 16 + 8 + c], t[c], acc);
+        }
+        acc += __shfl_xor(acc, 4, 64);
+        acc += __shfl_xor(acc, 2, 64);
+        acc += __shfl_xor(acc, 1, 64);
+        if (k < nk && part == 0) sc[k] = acc;
+    }
+    __syncthreads();
+    if (tid < 64) {   // statistics over <= 66 slots and <= 144 keys, strided over the 64 lanes of wave 0
+        float M = -INFINITY;
+        for (int s = tid; s < v.ns; s += 64) M = fmaxf(M, sml[0][s]);
+        for (int k = tid; k < nk; k += 64) M = fmaxf(M, sc[k]);
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) M = fmaxf(M, __shfl_xor(M, o, 64));
+        float Ls = 0.0f;
+        for (int s = tid; s < v.ns; s += 64) {
+            const float c = sml[0][s] == -INFINITY ? 0.0f : __expf(sml[0][s] - M);
+            coef[s] = c;
+            Ls = fmaf(c, sml[1][s], Ls);
+        }
+        for (int k = tid; k < nk; k += 64) {
+            const float c = __expf(sc[k] - M);
+            coef[RS_MAX + k] = c;
+            Ls += c;
+        }
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) Ls += __shfl_xor(Ls, o, 64);
+        if (tid == 0) { stat[0] = M; stat[1] = Ls; }
+    }
+    __syncthreads();
+    const int grp = tid >> 7, d = tid & (AD - 1);
+    float o = 0.0f;
+    for (int s = grp; s < v.ns; s += 2) o = fmaf(coef[s], v.part_o[(x * v.pslots + s) * AD + d], o);
+    for (int k = grp; k < nk; k += 2) {
+        const uint16_t* vr = k < v.Wm ? v.vwin + (bhk * v.wcap + k) * (int64_t)AD : v.vnew + (bhk * v.n + k - v.Wm) * (int64_t)AD;
+        o = fmaf(coef[RS_MAX + k], h2f_bits(vr[d]), o);
+    }
+    og[grp][d] = o;
+    __syncthreads();
+    if (tid < AD) {
+        v.out[x * AD + tid] = f2h_bits((og[0][tid] + og[1][tid]) / stat[1]);
+        if (v.lse && tid == 0) v.lse[x] = stat[0] + logf(stat[1]);
+    }
+}
+
+}  // namespace
+
+extern "C" size_t gear_attn_verify_workspace(int B, int Hq, int n, int T, int W) {
+    if (B <= 0 || Hq <= 0 || n <= 0 || T < 0 || W < 0) return 0;
+    return gear_attn_decode_workspace(B, Hq * n, T, 2);       // the partial slots of B Hq n query rows
+}
+
+extern "C" int gear_attn_verify_cache(const gear_cache_view* c, const void* q, int Hq, int n, int T, int W, const void* k_new,
+                                      const void* v_new, float qscale, void* out, void* lse, void* workspace, size_t workspace_bytes,
+                                      void* stream) {
+    GEAR_CHECK_ARG(c, "gear_attn_verify_cache: null cache view");
+    GEAR_CHECK_ARG(n >= 1 && n <= VN_MAX, "gear_attn_verify_cache: n = %d query tokens, must be in [1, %d] (longer chunks: "
+                   "gear_attn_extend_cache)", n, VN_MAX);
+    GEAR_CHECK_ARG(c->D == AD, "gear_attn_verify_cache: head_dim %d, must be 128", c->D);
+    GEAR_CHECK_ARG(c->B > 0 && c->Hkv > 0, "gear_attn_verify_cache: B %d x Hkv %d", c->B, c->Hkv);
+    GEAR_CHECK_ARG(Hq > 0 && Hq % c->Hkv == 0, "gear_attn_verify_cache: Hq %d not a multiple of Hkv %d", Hq, c->Hkv);
+    GEAR_CHECK_ARG((int64_t)c->B * Hq * n <= 65535, "gear_attn_verify_cache: B %d x Hq %d x n %d query rows", c->B, Hq, n);
+    GEAR_CHECK_ARG(W >= 0 && W <= c->wcap && c->wcap <= 128, "gear_attn_verify_cache: W = %d window tokens, the window holds "
+                   "wcap = %d (at most 128)", W, c->wcap);
+    GEAR_CHECK_ARG(T >= 0 && T <= c->tcap && T % 64 == 0,
+                   "gear_attn_verify_cache: T = %d compressed tokens, must be a multiple of 64 in [0, tcap = %d]", T, c->tcap);
+    GEAR_CHECK_ARG(q && k_new && v_new && out, "gear_attn_verify_cache: null q / k_new / v_new / out");
+    GEAR_CHECK_ARG(W == 0 || (c->kwin && c->vwin), "gear_attn_verify_cache: W > 0 needs the window tensors");
+    const size_t need = gear_attn_verify_workspace(c->B, Hq, n, T, W);
+    GEAR_CHECK_ARG(workspace && workspace_bytes >= need, "gear_attn_verify_cache: workspace of %zu bytes, needs %zu "
+                   "(gear_attn_verify_workspace)", workspace_bytes, need);
+    VerifyMerge m;
+    m.ns = 0;
+    m.pslots = 1;
+    m.part_o = m.part_ml = nullptr;
+    m.Wm = W;
+    if (T > 0) {      // the compressed part (+ the window, where the plan makes it a slot): decode partials of Hq n query rows
+        AttnArgs tmp, a;
+        StreamExtras ex;
+        view_to_args(c, tmp, ex);
+        int kk = 0;
+        if (c->koidx && c->koval) kk = c->kkb == 0 ? c->kk0 : c->kk_cap;
+        const int rc = attn_decode_impl(q, c->kcode, c->kscale, c->kmn, c->kP, c->kQ, c->koidx, c->koval, c->vcode, c->vscale,
+                                        c->vmn, c->vP, c->vQ, c->voidx, c->voval, c->kwin, c->vwin, c->B, Hq * n, c->Hkv, c->D, T, W,
+                                        c->ldk, c->lsk, c->tcap, c->tcap, c->tcap, c->group, c->bits, c->mode, c->rk, c->rv, kk, c->kv,
+                                        c->seg0, c->seglen, c->wcap, nullptr, qscale, out, lse, workspace, workspace_bytes, stream,
+                                        c->kochunk, c->vochunk, &ex, &a);
+        if (rc != 0) return rc;
+        m.ns = a.pslots;
+        m.pslots = a.pslots;
+        m.part_o = a.part_o;
+        m.part_ml = a.part_ml;
+        if (a.pslots != a.splits) m.Wm = 0;                  // the window rode along as the last slot
+    }
+    m.q = (const uint16_t*)q;
+    m.kwin = (const uint16_t*)c->kwin; m.vwin = (const uint16_t*)c->vwin; m.wcap = c->wcap;
+    m.knew = (const uint16_t*)k_new; m.vnew = (const uint16_t*)v_new;
+    m.Hq = Hq; m.Hkv = c->Hkv; m.n = n;
+    m.qscale = qscale;
+    m.out = (uint16_t*)out;
+    m.lse = (float*)lse;
+    hipLaunchKernelGGL(attn_verify_merge_kernel, dim3((unsigned)((int64_t)c->B * Hq * n)), dim3(256), 0, (hipStream_t)stream, m);
+    GEAR_CHECK_LAUNCH("attn_verify_merge");
+    return 0;
 }

@@ -282,6 +282,127 @@ class FastGearDecoder:
         self._state_dirty = True          # a later step_graph() brings the device-side state up to date
         return self.model.lm_head(m.norm(h))
 
+    # ------------------------------------------------------------------------------------------------ speculative verify
+    def _room(self) -> int:
+        """The most tokens the caches can still take (extend() / verify() refuse more)."""
+        c0 = self.layers[0]["cache"]
+        if self.pool is None:
+            return c0.R - c0.n_win
+        return (c0.Tmax - c0.n_comp) // c0.R * c0.R + c0.R - 1 - c0.n_win
+
+    @torch.no_grad()
+    def verify(self, input_ids: torch.Tensor) -> torch.Tensor:
+        """Check n <= N_MAX_VERIFY (16) tokens [B, n] after prefill() without committing them: step()'s projections over B n rows
+        (the fused GEMVs while B n <= 4), RoPE at pos .. pos + n - 1 and per layer cache.attend_verify (the decode kernels).  Returns the logits of every position [B, n, vocab]; every
+        layer's n post-RoPE K / V rows are kept until accept(m) commits rows 0 .. m - 1.  Changes no cache state."""
+        from .cache import N_MAX_VERIFY, _check_room
+        if self.tp_world > 1:
+            raise NotImplementedError("verify(): head-sharded (tp_world > 1) verification is not implemented -- use step()")
+        if torch.cuda.is_current_stream_capturing():
+            raise NotImplementedError("verify(): speculative verification cannot be captured in a graph (host-side counters)")
+        if self.pos == 0:
+            raise ValueError("verify(): run prefill() first")
+        if input_ids.dim() != 2 or input_ids.shape[0] != self.batch or not 1 <= input_ids.shape[1] <= N_MAX_VERIFY:
+            raise ValueError(f"verify(): input_ids must be [{self.batch}, n], 1 <= n <= {N_MAX_VERIFY} (longer chunks: extend()), "
+                             f"got {list(input_ids.shape)}")
+        B, n = input_ids.shape
+        c0 = self.layers[0]["cache"]
+        if self.pool is not None:
+            _check_room(c0, n)
+        elif c0.n_win + n > c0.R:
+            raise L.GearError(f"verify(): {n} tokens after {c0.n_win} exceed the fp16 cache's capacity {c0.R}")
+        self._pending = None
+        m = self.model.model
+        res = m.embed_tokens(input_ids).view(B * n, -1)          # the B n rows as step()'s batch rows
+        pos = torch.arange(self.pos, self.pos + n, device=self.dev).unsqueeze(0)
+        Hq, Hkv, D = self.Hq, self.Hkv, self.D
+        ks, vs = [], []
+        for lw in self.layers:
+            # step()'s projections over B n rows: the fused GEMVs (one launch each) while B n <= 4, the library GEMM beyond
+            qkv = self._norm_linear(res, lw["wqkv"]).view(B, n, -1)
+            q, k, v = qkv.split([Hq * D, Hkv * D, Hkv * D], dim=-1)
+            q = q.view(B, n, Hq, D).transpose(1, 2)
+            k = k.view(B, n, Hkv, D).transpose(1, 2)
+            v = v.reshape(B, n, Hkv, D).transpose(1, 2).contiguous()
+            cos, sin = lw["rotary"](v, pos)
+            q, k = apply_rotary_pos_emb(q, k, cos, sin)
+            q, k = q.contiguous(), k.contiguous()
+            a = lw["cache"].attend_verify(q, k, v)
+            ks.append(k)
+            vs.append(v)
+            res = self._linear_add(a.transpose(1, 2).reshape(B * n, Hq * D), lw["wo"], res)
+            act = self._norm_linear(res, lw["wgu"], swiglu=True)
+            res = self._linear_add(act, lw["wd"], res)
+        self._pending = dict(ks=ks, vs=vs, n=n, pos=self.pos)
+        return self._norm_linear(res, self.w_head).view(B, n, -1)
+
+    @torch.no_grad()
+    def accept(self, m: int) -> int:
+        """Commit rows 0 .. m - 1 (0 <= m <= n) of the last verify() to every layer's cache, exactly as extend() of those tokens
+        commits them (the windows fill, the pooled block compressor runs at each boundary); advances pos.  Returns m."""
+        p = getattr(self, "_pending", None)
+        if p is None or p["pos"] != self.pos:
+            raise ValueError("accept(): no pending verify() (each verify() can be accepted once, before any other step)")
+        if not 0 <= m <= p["n"]:
+            raise ValueError(f"accept(): m = {m}, the last verify() checked n = {p['n']} tokens")
+        self._pending = None
+        if m == 0:
+            return 0
+        ks = [k[:, :, :m] for k in p["ks"]]
+        vs = [v[:, :, :m] for v in p["vs"]]
+        if self.pool is not None:
+            for _ in range(self.pool.extend_all(ks, vs)):
+                self._after_boundary()
+        else:
+            for lw, k, v in zip(self.layers, ks, vs):
+                lw["cache"].extend(k, v)
+        self.pos += m
+        self._state_dirty = True          # a later step_graph() brings the device-side state up to date
+        return m
+
+    @torch.no_grad()
+    def generate_speculative(self, input_ids: torch.Tensor, max_length: int, draft="ngram", n_draft: int = 3,
+                             return_stats: bool = False):
+        """Greedy decoding with speculative verification: each pass drafts k <= n_draft tokens (draft = "ngram":
+        speculative.ngram_draft over the tokens so far, or a callable (tokens [B, L], k) -> [B, k]), verifies [last token, d1 .. dk]
+        in one verify() and commits the accepted drafts + the model's next token (accept(a + 1)).  With batch > 1 every row commits
+        the batch's minimum accepted length a: the caches stay rectangular and every row's tokens stay the greedy ones (a row whose
+        drafts ran longer re-proposes them next pass).  Returns [B, max_length] tokens as generate() does; with return_stats also
+        dict(passes, tokens, tokens_per_pass, drafted, accepted, acceptance_rate)."""
+        from .speculative import accepted_lengths, ngram_draft
+        if draft == "ngram":
+            drafter = ngram_draft
+        elif callable(draft):
+            drafter = draft
+        else:
+            raise ValueError(f"generate_speculative: draft {draft!r}: 'ngram' or a callable (tokens, k) -> [B, k]")
+        if n_draft < 0:
+            raise ValueError(f"generate_speculative: n_draft = {n_draft}")
+        from .cache import N_MAX_VERIFY
+        n_draft = min(n_draft, N_MAX_VERIFY - 1)
+        logits = self.prefill(input_ids)
+        out = torch.cat([input_ids, logits.argmax(-1, keepdim=True)], 1)
+        passes = drafted = accepted = 0
+        while out.shape[1] < max_length:
+            k = max(0, min(n_draft, max_length - out.shape[1] - 1, self._room() - 1))
+            d = drafter(out, k) if k else out.new_zeros((out.shape[0], 0))
+            d = d.to(device=out.device, dtype=out.dtype)
+            if tuple(d.shape) != (out.shape[0], k):
+                raise ValueError(f"generate_speculative: the drafter returned {list(d.shape)}, wanted [{out.shape[0]}, {k}]")
+            lg = self.verify(torch.cat([out[:, -1:], d], 1))
+            a = int(accepted_lengths(d, lg).min())
+            self.accept(a + 1)
+            out = torch.cat([out, lg[:, :a + 1].argmax(-1)], 1)      # = the accepted drafts, then the model's own token
+            passes += 1
+            drafted += k
+            accepted += a
+        self.check_block_kernel()
+        if not return_stats:
+            return out
+        gen = out.shape[1] - input_ids.shape[1]
+        return out, dict(passes=passes, tokens=gen, tokens_per_pass=(gen - 1) / max(passes, 1), drafted=drafted, accepted=accepted,
+                         acceptance_rate=accepted / max(drafted, 1))
+
     # ------------------------------------------------------------------------------------------------ decode
     @torch.no_grad()
     def step(self, token_ids: torch.Tensor) -> torch.Tensor:

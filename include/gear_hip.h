@@ -399,6 +399,20 @@ size_t gear_attn_extend_workspace(int B, int Hq, int n, int T, int W);
 int gear_attn_extend_cache(const gear_cache_view* c, const void* q, int Hq, int n, int T, int W, const void* k_new,
                            const void* v_new, float qscale, void* out, void* lse, void* workspace, size_t workspace_bytes,
                            void* stream);
+/* ---- speculative verify: n <= 16 draft tokens at once -----------------------------------------------------------------------
+ * gear_attn_extend_cache's semantics (query i over the T compressed tokens, the W window tokens and chunk rows 0 .. i, one fp32
+ * softmax, no cache state changes) for the draft sizes of speculative decoding, on the decode kernels: q goes to the decode
+ * partial dispatch as B x (Hq n) query rows of one token each (a KV head's G n rows share its compressed chunks), and one merge
+ * launch adds the window and the causal chunk rows.  Accepts every configuration gear_attn_decode_cache accepts (T == 0 and W == 0
+ * included); W + n may exceed wcap (the chunk rows are never written into the window).  The attention options apply as for decode,
+ * except attn_fold (the merge always runs in its own launch).
+ *   q      fp16 [B, Hq, n, 128] at positions T + W .. T + W + n - 1; k_new / v_new fp16 [B, Hkv, n, 128] (post-RoPE), 1 <= n <= 16
+ *   out    fp16 [B, Hq, n, 128]; lse optional float [B, Hq, n] (log-sum-exp of the scaled scores)
+ *   workspace: gear_attn_verify_workspace(B, Hq, n, T, W) bytes.  Two launches (one when T == 0). */
+size_t gear_attn_verify_workspace(int B, int Hq, int n, int T, int W);
+int gear_attn_verify_cache(const gear_cache_view* c, const void* q, int Hq, int n, int T, int W, const void* k_new,
+                           const void* v_new, float qscale, void* out, void* lse, void* workspace, size_t workspace_bytes,
+                           void* stream);
 /* (Re)build the sparse tiles of K chunks [k_chunk0, k_chunk1) (128 tokens each) and V blocks [v_blk0, v_blk1) (64 tokens each) of a
  * cache that holds T compressed tokens: called after the prompt and after every appended block (the chunk the block lies in). */
 int gear_cache_tiles_build(const gear_cache_view* c, int T, int k_chunk0, int k_chunk1, int v_blk0, int v_blk1, void* stream);
