@@ -87,6 +87,7 @@ SIGNATURES = {
     "gear_xchg_open": (_i, [_vp, C.POINTER(_vp)]),
     "gear_xchg_close": (_i, [_vp]),
     "gear_xchg_allgather": (_i, [_vp, _i, _sz, _i, _i, _vp, _vp, _vp, _vp]),
+    "gear_sample_tokens": (_i, [_vp, _i, _i, _i, _i64, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
 ABI_VERSION = 5      # what this table was written against (gear_abi_version() of the library must match)
@@ -174,6 +175,11 @@ class CacheView(C.Structure):
     _INTS = ("B", "Hkv", "D", "tcap", "ldk", "lsk", "group", "bits", "mode", "rk", "rv", "kk_cap", "kk0", "kkb", "kv", "seg0",
              "seglen", "wcap", "nbk_pitch", "ktile_cap", "nck", "vtile_cap", "nblk")
     _fields_ = [(n, C.c_void_p) for n in _PTRS] + [(n, C.c_int) for n in _INTS]
+
+
+class SampleParamsC(C.Structure):
+    """ctypes mirror of `gear_sample_params` (include/gear_hip.h)."""
+    _fields_ = [("temperature", C.c_float), ("top_k", C.c_int), ("top_p", C.c_float), ("reserved", C.c_int), ("seed", C.c_uint64)]
 
 
 def stream_ptr(t=None) -> int:

@@ -16,6 +16,7 @@ import torch.nn.functional as F
 from . import _lib as L
 from .cache import Fp16KVCache, GearKVCache, GearKVCachePool
 from .modeling_llamagear import apply_rotary_pos_emb
+from .sampling import sample_tokens
 
 
 class FastGearDecoder:
@@ -93,6 +94,9 @@ class FastGearDecoder:
         for lw in self.layers:
             lw["cache"].state = self.state
         self.graph = None
+        self.graph_sampled = None     # the sampled token step (step_graph_sampled) and the params it was captured with
+        self._graph_sampling = None
+        self.logits_sampled_static = None
         self._state_dirty = True      # host counters moved without the device-side state (eager step / prefill)
         self.tok = torch.zeros((batch, 1), dtype=torch.long, device=dev)
         self.logits_static = None
@@ -362,13 +366,17 @@ class FastGearDecoder:
 
     @torch.no_grad()
     def generate_speculative(self, input_ids: torch.Tensor, max_length: int, draft="ngram", n_draft: int = 3,
-                             return_stats: bool = False):
+                             return_stats: bool = False, sampling=None):
         """Greedy decoding with speculative verification: each pass drafts k <= n_draft tokens (draft = "ngram":
         speculative.ngram_draft over the tokens so far, or a callable (tokens [B, L], k) -> [B, k]), verifies [last token, d1 .. dk]
         in one verify() and commits the accepted drafts + the model's next token (accept(a + 1)).  With batch > 1 every row commits
         the batch's minimum accepted length a: the caches stay rectangular and every row's tokens stay the greedy ones (a row whose
         drafts ran longer re-proposes them next pass).  Returns [B, max_length] tokens as generate() does; with return_stats also
-        dict(passes, tokens, tokens_per_pass, drafted, accepted, acceptance_rate)."""
+        dict(passes, tokens, tokens_per_pass, drafted, accepted, acceptance_rate).
+        sampling (a sampling.SamplingParams): speculative sampling instead of greedy acceptance -- ONE gear_sample_tokens call over
+        the verify logits [B, k + 1, V] accepts draft d_i with probability p(d_i) at its position and otherwise draws from p without
+        d_i (the bonus row draws from p): every emitted token is an exact sample from the filtered distribution.  a = the batch
+        minimum of leading accepts; a row that accepted further emits its draft at a, a row rejected at a its residual draw."""
         from .speculative import accepted_lengths, ngram_draft
         if draft == "ngram":
             drafter = ngram_draft
@@ -381,7 +389,8 @@ class FastGearDecoder:
         from .cache import N_MAX_VERIFY
         n_draft = min(n_draft, N_MAX_VERIFY - 1)
         logits = self.prefill(input_ids)
-        out = torch.cat([input_ids, logits.argmax(-1, keepdim=True)], 1)
+        first = logits.argmax(-1, keepdim=True) if sampling is None else self._sample(logits, sampling)
+        out = torch.cat([input_ids, first], 1)
         passes = drafted = accepted = 0
         while out.shape[1] < max_length:
             k = max(0, min(n_draft, max_length - out.shape[1] - 1, self._room() - 1))
@@ -390,9 +399,19 @@ class FastGearDecoder:
             if tuple(d.shape) != (out.shape[0], k):
                 raise ValueError(f"generate_speculative: the drafter returned {list(d.shape)}, wanted [{out.shape[0]}, {k}]")
             lg = self.verify(torch.cat([out[:, -1:], d], 1))
-            a = int(accepted_lengths(d, lg).min())
-            self.accept(a + 1)
-            out = torch.cat([out, lg[:, :a + 1].argmax(-1)], 1)      # = the accepted drafts, then the model's own token
+            if sampling is None:
+                a = int(accepted_lengths(d, lg).min())
+                self.accept(a + 1)
+                out = torch.cat([out, lg[:, :a + 1].argmax(-1)], 1)      # = the accepted drafts, then the model's own token
+            else:
+                # row i of a sequence predicts position pos + 1 + i; its draft is d_{i+1}, none (-1) for the bonus row
+                B = out.shape[0]
+                dr = torch.cat([d, d.new_full((B, 1), -1)], 1).reshape(-1).long()
+                tok, acc, _ = sample_tokens(lg.reshape(B * (k + 1), -1), sampling, pos=self.pos + 1, n_per_seq=k + 1, draft=dr)
+                tok, acc = tok.view(B, k + 1), acc.view(B, k + 1)
+                a = int(acc[:, :k].long().cumprod(1).sum(1).min()) if k else 0
+                self.accept(a + 1)
+                out = torch.cat([out, tok[:, :a + 1].to(out.dtype)], 1)
             passes += 1
             drafted += k
             accepted += a
@@ -428,9 +447,10 @@ class FastGearDecoder:
         c = self.layers[0]["cache"]
         self.state.copy_(torch.tensor([self.pos, c.n_win, c.n_comp, c.n_win + 1], dtype=torch.int32))
 
-    def _step_body_dyn(self):
+    def _step_body_dyn(self, sampling=None):
         """The token step with every per-token scalar read from self.state on the device: identical launches for every
-        token, so the whole thing (embedding -> 32 layers -> lm_head -> argmax -> state advance) is one graph."""
+        token, so the whole thing (embedding -> 32 layers -> lm_head -> argmax -> state advance) is one graph.  With `sampling`
+        the argmax is gear_sample_tokens at position state.pos + 1 (read on the device before the advance)."""
         m = self.model.model
         res = m.embed_tokens(self.tok.view(-1))
         for lw in self.layers:
@@ -440,7 +460,10 @@ class FastGearDecoder:
             act = self._norm_linear(res, lw["wgu"], swiglu=True)
             res = self._linear_add(act, lw["wd"], res)
         logits = self._norm_linear(res, self.w_head)
-        self.tok.copy_(logits.argmax(-1, keepdim=True))
+        if sampling is None:
+            self.tok.copy_(logits.argmax(-1, keepdim=True))
+        else:
+            self.tok.copy_(sample_tokens(logits, sampling, pos=1, pos_dev=self.state)[0].view(-1, 1))
         L.check(L.load().gear_decode_state_advance(L.ptr(self.state), L.stream_ptr()), "gear_decode_state_advance")
         return logits
 
@@ -449,6 +472,16 @@ class FastGearDecoder:
         """One greedy decode token by replaying the captured graph.  token_ids (optional) overrides the token the graph
         produced itself; returns the NEXT token [B,1] (the graph's own argmax).  Block compression (every `residual`
         tokens) runs eagerly between replays."""
+        return self._graph_step(token_ids, None)
+
+    @torch.no_grad()
+    def step_graph_sampled(self, sampling, token_ids: torch.Tensor = None) -> torch.Tensor:
+        """step_graph() with gear_sample_tokens in place of the argmax: a graph of its own (self.graph_sampled, recaptured when
+        `sampling` differs from the params it was captured with); the greedy graph is left alone.  Draws depend on (seed,
+        sequence, position) only, so the tokens equal those of eager step() + sample_tokens at self.pos."""
+        return self._graph_step(token_ids, sampling)
+
+    def _graph_step(self, token_ids, sampling):
         if self.pool is None:
             raise NotImplementedError("step_graph(): the fp16-cache baseline has eager steps only")
         if self.gather is not None and not self.gather.capturable and not getattr(self, "_peer_tried", False):
@@ -468,18 +501,24 @@ class FastGearDecoder:
                                       "path copies through the host) -- use step()")
         if token_ids is not None:
             self.tok.copy_(token_ids.view(self.batch, 1))
-        if self.graph is None:
+        if sampling is not None and self.graph_sampled is not None and self._graph_sampling != sampling:
+            self.graph_sampled = None        # other params: capture again
+        graph = self.graph if sampling is None else self.graph_sampled
+        if graph is None:
             self._sync_state()
             self._state_dirty = False
             torch.cuda.synchronize()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                self.logits_static = self._step_body_dyn()
-            self.graph = g
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph):
+                logits = self._step_body_dyn(sampling)
+            if sampling is None:
+                self.graph, self.logits_static = graph, logits
+            else:
+                self.graph_sampled, self._graph_sampling, self.logits_sampled_static = graph, sampling, logits
         elif self._state_dirty:          # an eager step() / prefill() ran since the last replay: bring the device state up to date
             self._sync_state()
         self._state_dirty = False
-        self.graph.replay()
+        graph.replay()
         self.pos += 1
         full = False
         for lw in self.layers:
@@ -497,8 +536,16 @@ class FastGearDecoder:
         if self.gather is not None and hasattr(self.gather, "close"):
             self.gather.close()
 
+    def _sample(self, logits, sampling):
+        """The next token [B, 1] from logits [B, V] at position self.pos (the one after the last token fed)."""
+        return sample_tokens(logits, sampling, pos=self.pos)[0].view(-1, 1)
+
     @torch.no_grad()
-    def generate(self, input_ids: torch.Tensor, max_length: int, graph: bool = False) -> torch.Tensor:
+    def generate(self, input_ids: torch.Tensor, max_length: int, graph: bool = False, sampling=None) -> torch.Tensor:
+        """Greedy decoding; with `sampling` (a sampling.SamplingParams) every token is drawn by gear_sample_tokens at its own
+        position -- the first from the prefill logits, the rest from step()'s (graph=True: step_graph_sampled(), same tokens)."""
+        if sampling is not None:
+            return self._generate_sampled(input_ids, max_length, graph, sampling)
         logits = self.prefill(input_ids)
         out = [input_ids]
         nxt = logits.argmax(-1, keepdim=True)
@@ -512,6 +559,25 @@ class FastGearDecoder:
                 nxt = self.step_graph().clone()
             else:
                 nxt = self.step(nxt).argmax(-1, keepdim=True)
+            out.append(nxt)
+        self.check_exchange()
+        self.check_block_kernel()
+        return torch.cat(out, dim=1)
+
+    def _generate_sampled(self, input_ids, max_length, graph, sampling):
+        logits = self.prefill(input_ids)
+        out = [input_ids]
+        nxt = self._sample(logits, sampling)
+        out.append(nxt)
+        if graph and sum(t.shape[1] for t in out) < max_length:
+            nxt = self._sample(self.step(nxt), sampling)        # one eager step warms up every library handle
+            out.append(nxt)
+            self.tok.copy_(nxt)
+        while sum(t.shape[1] for t in out) < max_length:
+            if graph:
+                nxt = self.step_graph_sampled(sampling).clone()
+            else:
+                nxt = self._sample(self.step(nxt), sampling)
             out.append(nxt)
         self.check_exchange()
         self.check_block_kernel()

@@ -171,13 +171,13 @@ class MistralForCausalLM_GEAR(LlamaForCausalLM_GEARKIVI):
     the same compress hook to MistralAttention.  Contexts up to the sliding window."""
 
     @torch.no_grad()
-    def generate(self, input_ids, max_length: int, use_cache: bool = True):
+    def generate(self, input_ids, max_length: int, use_cache: bool = True, **sampling):
         _check_window(self.config, max_length)
-        return super().generate(input_ids, max_length, use_cache)
+        return super().generate(input_ids, max_length, use_cache, **sampling)
 
 
 class MistralForCausalLM_KIVI(LlamaForCausalLM_KIVI):
     @torch.no_grad()
-    def generate(self, input_ids, max_length: int, use_cache: bool = True):
+    def generate(self, input_ids, max_length: int, use_cache: bool = True, **sampling):
         _check_window(self.config, max_length)
-        return super().generate(input_ids, max_length, use_cache)
+        return super().generate(input_ids, max_length, use_cache, **sampling)

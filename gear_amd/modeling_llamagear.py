@@ -34,6 +34,7 @@ from torch import nn
 
 from . import _lib as L
 from .quant.matmul import cuda_bmm_fA_qB_outer
+from .sampling import SamplingParams, sample_tokens
 from .quant.new_pack import (headwise_lrap, triton_quantize_and_pack_along_last_dim,
                              triton_quantize_and_pack_along_last_dim_witherror)
 
@@ -978,7 +979,12 @@ class LlamaForCausalLM_GEARKIVI(nn.Module):
         return self.lm_head(h), presents
 
     @torch.no_grad()
-    def generate(self, input_ids, max_length: int, use_cache: bool = True):
+    def generate(self, input_ids, max_length: int, use_cache: bool = True, do_sample: bool = False, temperature: float = 1.0,
+                 top_k: int = 50, top_p: float = 1.0, seed: int = 0):
+        """Greedy by default; do_sample=True samples with HF's generate() kwargs and defaults (temperature, top_k, top_p) through
+        gear_sample_tokens (sampling.py), the token at position P drawn from the (seed, sequence, P) random stream."""
+        if do_sample:
+            return self._generate_sampled(input_ids, max_length, SamplingParams(temperature, top_k, top_p, seed))
         logits, past = self.forward(input_ids, None, True)
         out = [input_ids]
         nxt = logits[:, -1].argmax(-1, keepdim=True)
@@ -986,5 +992,18 @@ class LlamaForCausalLM_GEARKIVI(nn.Module):
         while sum(t.shape[1] for t in out) < max_length:
             logits, past = self.forward(nxt, past, True)
             nxt = logits[:, -1].argmax(-1, keepdim=True)
+            out.append(nxt)
+        return torch.cat(out, dim=1)
+
+    def _generate_sampled(self, input_ids, max_length: int, params):
+        logits, past = self.forward(input_ids, None, True)
+        out = [input_ids]
+        n = input_ids.shape[1]
+        nxt = sample_tokens(logits[:, -1], params, pos=n)[0].view(-1, 1)
+        out.append(nxt)
+        while n + 1 < max_length:
+            logits, past = self.forward(nxt, past, True)
+            n += 1
+            nxt = sample_tokens(logits[:, -1], params, pos=n)[0].view(-1, 1)
             out.append(nxt)
         return torch.cat(out, dim=1)

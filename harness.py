@@ -80,16 +80,25 @@ def run(variant, args, dev):
     torch.cuda.reset_peak_memory_stats(dev)
     torch.cuda.synchronize()
     t0 = time.time()
+    # --do_sample: HF's generate(do_sample=True, temperature, top_k, top_p) through gear_sample_tokens; without it the greedy path
+    sampling = None
+    hook_kw = {}
+    if args.do_sample:
+        from gear_amd.sampling import SamplingParams
+        sampling = SamplingParams(args.temperature, args.top_k, args.top_p, args.seed)
+        hook_kw = dict(do_sample=True, temperature=args.temperature, top_k=args.top_k, top_p=args.top_p, seed=args.seed)
+    fast_kw = {} if sampling is None else dict(sampling=sampling)
     if variant == "gearl" and args.fast:
         from gear_amd.fast_decode import FastGearDecoder
-        out = FastGearDecoder(model, args.max_length + 8, batch=args.batch_size).generate(ids, args.max_length)
+        out = FastGearDecoder(model, args.max_length + 8, batch=args.batch_size).generate(ids, args.max_length, **fast_kw)
     elif variant == "None" and args.fast:
         # the control through the SAME decoder (fused GEMVs, gear_attn_decode_f16 over cache.Fp16KVCache): gearl and None then
         # differ in the cache only
         from gear_amd.fast_decode import FastGearDecoder
-        out = FastGearDecoder(model, args.max_length + 8, batch=args.batch_size, cache_kind="fp16").generate(ids, args.max_length)
+        out = FastGearDecoder(model, args.max_length + 8, batch=args.batch_size, cache_kind="fp16").generate(ids, args.max_length,
+                                                                                                             **fast_kw)
     else:
-        out = model.generate(ids, args.max_length)
+        out = model.generate(ids, args.max_length, **hook_kw)
     torch.cuda.synchronize()
     dt = time.time() - t0
     peak = torch.cuda.max_memory_allocated(dev) / 2 ** 20
@@ -99,7 +108,9 @@ def run(variant, args, dev):
     del model
     torch.cuda.empty_cache()
     return dict(variant=variant, fast=bool(args.fast and variant in ("gearl", "None")), batch_size=args.batch_size, prompt_len=args.prompt_len,
-                max_length=int(out.shape[1]), time_s=dt, new_tokens_per_s=new / dt, peak_mem_MiB=peak, layers=args.layers)
+                max_length=int(out.shape[1]), time_s=dt, new_tokens_per_s=new / dt, peak_mem_MiB=peak, layers=args.layers,
+                **(dict(do_sample=True, temperature=args.temperature, top_k=args.top_k, top_p=args.top_p, seed=args.seed)
+                   if args.do_sample else {}))
 
 
 def main():
@@ -119,6 +130,12 @@ def main():
     ap.add_argument("--layers", type=int, default=32)
     ap.add_argument("--fast", action="store_true", help="GEAR through FastGearDecoder (pre-allocated cache, fused kernels)")
     ap.add_argument("--json", action="store_true")
+    # sampling, with the defaults of GenerationBench/GenerationTest/evaluation_bbh_cot.py:381-390
+    ap.add_argument("--do_sample", action="store_true", help="sample (temperature / top-k / top-p) instead of greedy decoding")
+    ap.add_argument("--temperature", type=float, default=0.8)
+    ap.add_argument("--top_k", type=int, default=50)
+    ap.add_argument("--top_p", type=float, default=0.95)
+    ap.add_argument("--seed", type=int, default=0, help="key of the sampler's random stream")
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)

@@ -487,6 +487,35 @@ int gear_gemv_qkv_rope(const void* x, const void* delta, const void* norm_w, flo
                        int Hq, int Hkv, int D, int pos, int slot, int wcap, float theta, const void* dyn_state,
                        void* res_out, void* q_out, void* kwin, void* vwin, void* stream);
 
+/* ---- token sampling: temperature, top-k, top-p and speculative accept / residual in ONE launch ------------------------------
+ * The decoders' replacement for the argmax (HF's generate(do_sample=True, temperature, top_k, top_p), the settings the reference
+ * evaluates with: GenerationBench/GenerationTest/evaluation_bbh_cot.py:381-390).  One workgroup per row; never synchronises or
+ * allocates (graph-capturable).
+ *   logits  fp16 [rows, V] (fp32 when logits_fp32), row stride ld >= V elements; 1 <= V <= 262144
+ *   row r   belongs to sequence b = r / n_per_seq at position P = pos + r % n_per_seq, pos = *pos_dev + pos0 (pos_dev: device int32,
+ *           e.g. the decode state {pos, ...}) or pos0 when pos_dev is NULL
+ *   params  (host pointer) temperature >= 0, top_k >= 0 (0 or >= V: off), top_p in (0, 1] (1: off), seed
+ *   draft   optional int64 [rows]: the drafted token of the row, -1 = none;  u optional float [rows][2]: (draw, accept) uniforms
+ *           in place of the generator
+ *   token_out int64 [rows]; accepted_out optional int32 [rows] (1: the draft was accepted); logprob_out optional float [rows]
+ *           (log p of the emitted token under the filtered distribution; 0 for temperature 0)
+ * Semantics (HF warper order): temperature 0 = argmax (first index), a draft accepted iff it equals it.  Otherwise
+ * x = fp32(logit) / temperature, -inf never kept; top-k keeps x >= the k-th largest x (edge ties kept); top-p keeps x_i iff the
+ * softmax mass (over the kept set) of the values > x_i is < top_p; e_j = exp(x_j - max), Z = sum over the kept set; the draw is the
+ * smallest kept index whose running sum in index order exceeds u_draw Z.  Draft rows: accept iff u_acc < e_d / Z; a rejected row
+ * draws over the kept set without d.  Uniforms: Philox4x32-10, key (seed lo, seed hi), counter (P, b, 0 = draw / 1 = accept, 0),
+ * u = (out[0] >> 8) 2^-24 -- a pure function of (seed, sequence, position, logits).  Integer sums only: bit-reproducible. */
+typedef struct {
+    float temperature;
+    int top_k;
+    float top_p;
+    int reserved;
+    uint64_t seed;
+} gear_sample_params;
+int gear_sample_tokens(const void* logits, int logits_fp32, int rows, int V, int64_t ld, int n_per_seq,
+                       const gear_sample_params* p, const int* pos_dev, int pos0, const int64_t* draft, const float* u,
+                       int64_t* token_out, int32_t* accepted_out, float* logprob_out, void* stream);
+
 /* ---- the exchange step of the head-sharded decode path (the reference has no distributed code) -------
  * With the KV heads split across ranks (one process per GPU) the only data any rank needs from the others is their slice of
  * the attention output in front of o_proj (cuda_supported_gear/modeling_llamagear.py:478-482 merges the heads).  Instead of a
