@@ -435,6 +435,7 @@ class GearKVCache:
         self._ws = None
         self._xws = None
         self._vws = None
+        self._sws = None
         self.use_tiles = True     # tests switch these off to compare the list paths
         self.use_chunk_index = True
         self._views = {}
@@ -587,6 +588,46 @@ class GearKVCache:
                                         1.0 / math.sqrt(self.D), L.ptr(out), L.ptr(lse), L.ptr(self._vws), self._vws.numel(),
                                         L.stream_ptr(q))
         L.check(rc, "gear_attn_verify_cache")
+        return (out, lse) if return_lse else out
+
+    def attend_shared(self, q: torch.Tensor, prefix: "GearKVCache", return_lse: bool = False):
+        """Shared-prefix decode attention: this cache (batch S) holds what each of S sequences appended after ONE common prompt,
+        `prefix` (a GearKVCache with batch 1, an empty window and the same compress config) holds that prompt's compressed tokens.
+        q fp16 [S,Hq,1,128] -> fp16 [S,Hq,1,128]: row (s, hq) is one fp32 softmax over the prefix's tokens, then sequence s's
+        compressed tokens, then its window (gear_attn_decode_shared; with return_lse also the fp32 [S,Hq] log-sum-exp).  Changes
+        no state of either cache.  use_tiles / use_chunk_index of this cache apply to both views."""
+        if not isinstance(prefix, GearKVCache) or prefix.B != 1 or prefix.n_win != 0:
+            raise ValueError("attend_shared: prefix must be a GearKVCache with batch 1 and an empty window")
+        if (prefix.H, prefix.D, prefix.bits, prefix.group, prefix.R, prefix.rk, prefix.rv, prefix.kv, prefix.kk_blk) != \
+                (self.H, self.D, self.bits, self.group, self.R, self.rk, self.rv, self.kv, self.kk_blk):
+            raise ValueError("attend_shared: prefix and tail caches were built with different compress configs / head counts")
+        S, Hq = q.shape[0], q.shape[1]
+        if tuple(q.shape) != (self.B, Hq, 1, self.D) or q.dtype != torch.float16:
+            raise ValueError(f"attend_shared: q must be fp16 [{self.B}, Hq, 1, {self.D}], got {list(q.shape)} {q.dtype}")
+        lib = L.load()
+        q = q.contiguous()
+        L.require_gpu(q)
+        out = torch.empty((S, Hq, 1, self.D), dtype=torch.float16, device=q.device)
+        lse = torch.empty((S, Hq), dtype=torch.float32, device=q.device) if return_lse else None
+        wsb = lib.gear_attn_decode_shared_workspace(S, Hq, prefix.Tmax, self.Tmax, self.bits)
+        if self._sws is None or self._sws.numel() < wsb:
+            self._sws = torch.empty((wsb,), dtype=torch.uint8, device=q.device)
+        views = []
+        for c, win in ((prefix, False), (self, True)):
+            key = (c.kk0, c.seg0, win, self.use_tiles, self.use_chunk_index)
+            view = c._views.get(key)
+            if view is None:
+                view = _view(c.bufs, c.dims, c.B, c.H, c.D, c.kk0, c.seg0, kwin=win)
+                if not self.use_tiles:
+                    view.ktile = view.vtile = None
+                if not self.use_chunk_index:
+                    view.kochunk = view.vochunk = None
+                c._views[key] = view
+            views.append(view)
+        rc = lib.gear_attn_decode_shared(C_.byref(views[0]), prefix.n_comp, C_.byref(views[1]), self.n_comp, self.n_win, L.ptr(q),
+                                         Hq, 1.0 / math.sqrt(self.D), L.ptr(out), L.ptr(lse), L.ptr(self._sws), self._sws.numel(),
+                                         L.stream_ptr(q))
+        L.check(rc, "gear_attn_decode_shared")
         return (out, lse) if return_lse else out
 
     def extend(self, k_new: torch.Tensor, v_new: torch.Tensor):

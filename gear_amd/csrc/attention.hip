@@ -86,8 +86,32 @@ struct AttnArgs {
     int fold;
     uint32_t* arrive;        // [B*Hq] arrival counters (zero between launches: the merging workgroup resets its head's)
     uint16_t* out_fold;      // [B*Hq, 128]
+    // shared-prefix launch (gear_attn_decode_shared; sh_S == 0: every other launch): B == 1, Hq counts the launch's rows S * (true Hq),
+    // ordered [KV head][query head of the group (sh_G of them)][sequence (sh_S)] -- the sh_G * sh_S rows of a KV head are consecutive,
+    // so a workgroup's NREP consecutive rows share its chunk; the partial slots are indexed by that row, q stays [S, Hq, 128] and
+    // q_row() maps a row to it
+    int sh_S, sh_G;
 };
+// the row of a.q that launch row x reads
+__device__ __forceinline__ int64_t q_row(const AttnArgs& a, int64_t x) {
+    if (a.sh_S == 0) return x;
+    const uint32_t P = (uint32_t)(a.sh_G * a.sh_S), xu = (uint32_t)x;
+    const uint32_t hkv = xu / P, p = xu % P, g = p / (uint32_t)a.sh_S, sq = p % (uint32_t)a.sh_S;
+    return (int64_t)sq * ((int64_t)a.Hkv * a.sh_G) + hkv * (uint32_t)a.sh_G + g;
+}
 __device__ __forceinline__ uint32_t div_sh(uint32_t x, int d, int sh) { return sh >= 0 ? x >> sh : x / (uint32_t)d; }
+
+// Order-independent sums of the outlier corrections (the DET instantiations of the vector kernels, taken by
+// gear_attn_decode_shared): the terms arrive through LDS atomics in whatever order the waves run, and a float sum would carry that
+// order into its last bits -- enough to move a sampled token that lies at a CDF boundary, so two runs with one seed could part.
+// Here every term is rounded to a multiple of 2^-32 on its own and the sum is a 64-bit integer sum: the same bits in any order.  A
+// term's rounding error (< 2^-32) is below the float spacing of any term above 2^-9 and eight decimal orders below ROW_BOUND; sums
+// stay exact up to 2^31, far beyond any score or unnormalised output (|p| <= 1) of an fp16 model.
+typedef long long osum_t;
+__device__ __forceinline__ void osum_add(osum_t* p, float v) {
+    atomicAdd((unsigned long long*)p, (unsigned long long)(long long)(v * 4294967296.0f));
+}
+__device__ __forceinline__ float osum_get(osum_t x) { return (float)x * (1.0f / 4294967296.0f); }
 
 __device__ __forceinline__ float block_reduce_max(float v, float* red) {
 #pragma unroll
@@ -164,7 +188,7 @@ __device__ __forceinline__ void k_list_ranges(const AttnArgs& a, const uint16_t*
 }
 
 
-template <int BITS, typename ST>
+template <int BITS, typename ST, bool DET = false>
 __global__ __launch_bounds__(256) void attn_decode_partial_kernel(AttnArgs a) {
     constexpr int CPW = 32 / BITS;
     constexpr uint32_t MASK = (1u << BITS) - 1u;
@@ -176,6 +200,8 @@ __global__ __launch_bounds__(256) void attn_decode_partial_kernel(AttnArgs a) {
     __shared__ float oacc[AD];
     __shared__ float wacc[4][MAXSEG][16];   // one copy per wave, merged in a fixed order
     __shared__ float red[4];
+    __shared__ osum_t sd[DET ? TC_MAX : 1];  // DET: the outlier terms of s[] / oacc[] as integer sums (osum_add)
+    __shared__ osum_t od[DET ? AD : 1];
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int split = blockIdx.x;
@@ -199,14 +225,15 @@ __global__ __launch_bounds__(256) void attn_decode_partial_kernel(AttnArgs a) {
     const ST* vmn = (const ST*)a.vmn;
 
     if (tid < AD) {
-        qs[tid] = h2f_bits(a.q[bhq * AD + tid]) * a.qscale;
+        qs[tid] = h2f_bits(a.q[q_row(a, bhq) * AD + tid]) * a.qscale;
         oacc[tid] = 0.0f;
+        if (DET) od[tid] = 0;
     }
     // factor segments touched by this chunk
     auto seg_of = [&](int t) { return (a.seglen == 0 || t < a.seg0) ? 0 : 1 + (t - a.seg0) / a.seglen; };
     const int seg_first = seg_of(t0), nseg_c = seg_of(t0 + tn - 1) - seg_first + 1;
     for (int i = tid; i < 4 * MAXSEG * 16; i += 256) (&wacc[0][0][0])[i] = 0.0f;
-    for (int i = tid; i < a.tc; i += 256) s[i] = 0.0f;
+    for (int i = tid; i < a.tc; i += 256) { s[i] = 0.0f; if (DET) sd[i] = 0; }
     __syncthreads();
     // u[seg] = Pk[seg]^T q: one factor row (rk contiguous fp16) per thread, reduced over the 128 channels with
     // wave shuffles + one LDS add per wave (the serial 128-deep load loop it replaces dominated small chunks)
@@ -327,7 +354,8 @@ __global__ __launch_bounds__(256) void attn_decode_partial_kernel(AttnArgs a) {
                     const float sc = ld_st<ST>(kscale + (bhk * AD + d) * (int64_t)a.lsk + g);
                     const float mnv = ld_st<ST>(kmn + (bhk * AD + d) * (int64_t)a.lsk + g);
                     const float deq = fmaf(sc, (float)((word >> (BITS * (t % CPW))) & MASK), mnv);
-                    atomicAdd(&s[t - t0], qd * (h2f_bits(ov[i]) - deq));
+                    if constexpr (DET) osum_add(&sd[t - t0], qd * (h2f_bits(ov[i]) - deq));
+                    else atomicAdd(&s[t - t0], qd * (h2f_bits(ov[i]) - deq));
                 }
             }
         }
@@ -335,7 +363,10 @@ __global__ __launch_bounds__(256) void attn_decode_partial_kernel(AttnArgs a) {
     __syncthreads();
     // ------------------------------------------------------------------ 2. chunk softmax statistics
     float lm = -INFINITY;
-    for (int t = tid; t < tn; t += 256) lm = fmaxf(lm, s[t]);
+    for (int t = tid; t < tn; t += 256) {
+        if (DET) s[t] += osum_get(sd[t]);           // (the same thread reads s[t] again below)
+        lm = fmaxf(lm, s[t]);
+    }
     const float m = block_reduce_max(lm, red);
     float ls = 0.0f;
     for (int t = tid; t < tn; t += 256) {
@@ -435,7 +466,8 @@ __global__ __launch_bounds__(256) void attn_decode_partial_kernel(AttnArgs a) {
                     const float sc = ld_st<ST>(vscale + row * ngv + d / a.group);
                     const float mnv = ld_st<ST>(vmn + row * ngv + d / a.group);
                     const float deq = fmaf(sc, (float)((word >> (BITS * (d % CPW))) & MASK), mnv);
-                    atomicAdd(&oacc[d], p * (h2f_bits(ov[i]) - deq));
+                    if constexpr (DET) osum_add(&od[d], p * (h2f_bits(ov[i]) - deq));
+                    else atomicAdd(&oacc[d], p * (h2f_bits(ov[i]) - deq));
                 }
             }
         }
@@ -445,6 +477,7 @@ __global__ __launch_bounds__(256) void attn_decode_partial_kernel(AttnArgs a) {
 #define WSUM(sl, c) ((wacc[0][sl][c] + wacc[1][sl][c]) + (wacc[2][sl][c] + wacc[3][sl][c]))
     if (tid < AD) {
         float o = oacc[tid];
+        if (DET) o += osum_get(od[tid]);
         for (int sl = 0; sl < nseg_c && a.rv > 0; sl++) {
             const uint16_t* pv = a.vP + (int64_t)(seg_first + sl) * a.vP_seg_stride + (bhk * AD + tid) * a.rv;
             if (a.rv == 8) {
@@ -722,8 +755,9 @@ __device__ __forceinline__ void dq_fma_word(uint32_t w, float sa24, float (&acc)
 }
 constexpr float DQ_2P24 = 16777216.0f;
 
-template <int BITS, typename ST, int RS, int NREP>
+template <int BITS, typename ST, int RS, int NREP, bool DET = false>
 __global__ __launch_bounds__(256, NREP == 1 ? 5 : 1) void attn_decode_partial_small(AttnArgs a) {
+    using OS = std::conditional_t<DET, osum_t, float>;   // DET: every outlier sum is an integer sum (osum_add), tiles and lists
     constexpr bool R16 = RS == 16;
     constexpr int RW = R16 ? 16 : 8;   // factor row width the arithmetic runs at
     constexpr int CPW = 32 / BITS;
@@ -744,8 +778,10 @@ __global__ __launch_bounds__(256, NREP == 1 ? 5 : 1) void attn_decode_partial_sm
     __shared__ float oacc[AD];
     __shared__ float wsl[2][RW];      // Qv^T p of the two slabs
     __shared__ float red[8];         // [0..3]: chunk maximum per wave, [4..7]: exponent sum per wave
-    __shared__ float ksp[SC];        // K outliers through the sparse tile: sum of q[d] (value - dequant) per token
-    __shared__ float vsp[AD];        // V outliers through the sparse tiles: sum of p[t] (value - dequant) per channel
+    __shared__ OS ksp[SC];           // K outliers through the sparse tile: sum of q[d] (value - dequant) per token
+    __shared__ OS vsp[AD];           // V outliers through the sparse tiles: sum of p[t] (value - dequant) per channel
+    auto oadd = [](OS* p, float v) { if constexpr (DET) osum_add(p, v); else atomicAdd(p, v); };
+    auto oget = [](OS x) { if constexpr (DET) return osum_get(x); else return x; };
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     // grid (heads of a batch entry -- query heads, or KV heads when a workgroup serves a group --, chunks, batch): no division, and
@@ -791,7 +827,8 @@ __global__ __launch_bounds__(256, NREP == 1 ? 5 : 1) void attn_decode_partial_sm
     const int seg_s0 = seg_at(t0), seg_s1 = seg_at(min(t0 + 64, t0 + tn - 1));
     float qvr[NREP];                   // this thread's channel of every query head of the group
 #pragma unroll
-    for (int r = 0; r < NREP; r++) qvr[r] = h2f_bits(a.q[(bhq0 + r) * AD + dq]) * a.qscale;
+    // (a shared-prefix launch takes this kernel with one row per workgroup only: the grouped instantiations keep their plain rows)
+    for (int r = 0; r < NREP; r++) qvr[r] = h2f_bits(a.q[(NREP == 1 ? q_row(a, bhq0) : bhq0 + r) * AD + dq]) * a.qscale;
     const int lw = tid & (NWC - 1), dsub = tid / NWC;
     const bool kval = lw * CPW < tn;
     // Addresses = uniform 64-bit base (head / chunk, scalar registers) + a 32-bit lane offset; lanes past the end of a partial
@@ -892,8 +929,8 @@ __global__ __launch_bounds__(256, NREP == 1 ? 5 : 1) void attn_decode_partial_sm
     // 21.1 -> see DESIGN.md section 6).  Tiles that overflowed (count -1) and payloads without tiles take the list paths below.
     const bool ktile_ok = a.kk > 0 && has_ktile && kc_raw >= 0;
     const bool vtile_ok = a.kv > 0 && has_vtile && vc_raw0 >= 0 && (tn <= 64 || vc_raw1 >= 0);
-    if (tid < SC) ksp[tid] = 0.0f;
-    if (tid < AD) vsp[tid] = 0.0f;
+    if (tid < SC) ksp[tid] = OS(0);
+    if (tid < AD) vsp[tid] = OS(0);
     // ------------------------------------------------------------------ 1. scores
     if (tid < AD) qs[tid] = qv;
     if (a.rk) {   // up[wave][:] = sum over this wave's 64 channels of q[d] Pk[seg(slab)][d][:]
@@ -914,12 +951,12 @@ __global__ __launch_bounds__(256, NREP == 1 ? 5 : 1) void attn_decode_partial_sm
     __syncthreads();
     if (ktile_ok) {   // chunk-major tile: ksp[t] += q[d] * (value - dequant), entries prefetched with everything else
         const int kc_n = kc_raw;
-        if (tid < kc_n) atomicAdd(&ksp[(ke0 >> 7) & 127u], qs[ke0 & 127u] * h2f_bits((uint16_t)(ke0 >> 16)));
-        if (tid + 256 < kc_n) atomicAdd(&ksp[(ke1 >> 7) & 127u], qs[ke1 & 127u] * h2f_bits((uint16_t)(ke1 >> 16)));
+        if (tid < kc_n) oadd(&ksp[(ke0 >> 7) & 127u], qs[ke0 & 127u] * h2f_bits((uint16_t)(ke0 >> 16)));
+        if (tid + 256 < kc_n) oadd(&ksp[(ke1 >> 7) & 127u], qs[ke1 & 127u] * h2f_bits((uint16_t)(ke1 >> 16)));
         const uint32_t* kt = a.ktile + (bhk * a.nck + split) * (int64_t)a.ktile_cap;
         for (int e = tid + 512; e < kc_n; e += 256) {
             const uint32_t ke = kt[e];
-            atomicAdd(&ksp[(ke >> 7) & 127u], qs[ke & 127u] * h2f_bits((uint16_t)(ke >> 16)));
+            oadd(&ksp[(ke >> 7) & 127u], qs[ke & 127u] * h2f_bits((uint16_t)(ke >> 16)));
         }
     }
     {
@@ -954,7 +991,7 @@ __global__ __launch_bounds__(256, NREP == 1 ? 5 : 1) void attn_decode_partial_sm
             }
             v += acc;
         }
-        if (ktile_ok) v += ksp[tid];
+        if (ktile_ok) v += oget(ksp[tid]);
         sv = v;
     }
     if (a.kk > 0 && !ktile_ok) {   // K outliers inside the chunk through the lists: s[t] += q[d] (val - dequant(t, d))
@@ -998,7 +1035,8 @@ __global__ __launch_bounds__(256, NREP == 1 ? 5 : 1) void attn_decode_partial_sm
                     if (tt[j] < t0 + tn && tt[j] >= t0) {
                         const int t = tt[j];
                         const float deq = fmaf(sc[j], (float)((word[j] >> (BITS * (t % CPW))) & MASK), mnv[j]);
-                        atomicAdd(&s[t - t0], qv * (val[j] - deq));
+                        if constexpr (DET) osum_add(&ksp[t - t0], qv * (val[j] - deq));    // (ksp: zero, no tile adds on this path)
+                        else atomicAdd(&s[t - t0], qv * (val[j] - deq));
                     }
                 }
                 if (tt[3] >= t0 + tn) break;   // (without the chunk index: stop at the first entry past the chunk)
@@ -1006,7 +1044,7 @@ __global__ __launch_bounds__(256, NREP == 1 ? 5 : 1) void attn_decode_partial_sm
             }
         }
         __syncthreads();
-        if (tid < SC) sv = s[tid];
+        if (tid < SC) sv = DET ? sv + oget(ksp[tid]) : s[tid];
     }
     // ------------------------------------------------------------------ 2. chunk softmax statistics
     // (two arrays and no leading barriers: red[0..3] was last read before the previous barrier of this pass, red[4..7] before the
@@ -1018,14 +1056,14 @@ __global__ __launch_bounds__(256, NREP == 1 ? 5 : 1) void attn_decode_partial_sm
     // ------------------------------------------------------------------ 3. V side
     if (vtile_ok) {   // block tiles: vsp[d] += p[t] * (value - dequant); read after the barriers of the dense part below
         const int vc_n0 = vc_raw0, vc_n1 = (tn > 64) ? vc_raw1 : 0;
-        if (tid < vc_n0) atomicAdd(&vsp[(ve0 >> 6) & 127u], s[ve0 & 63u] * h2f_bits((uint16_t)(ve0 >> 16)));
-        if (tid < vc_n1) atomicAdd(&vsp[(ve1 >> 6) & 127u], s[64 + (ve1 & 63u)] * h2f_bits((uint16_t)(ve1 >> 16)));
+        if (tid < vc_n0) oadd(&vsp[(ve0 >> 6) & 127u], s[ve0 & 63u] * h2f_bits((uint16_t)(ve0 >> 16)));
+        if (tid < vc_n1) oadd(&vsp[(ve1 >> 6) & 127u], s[64 + (ve1 & 63u)] * h2f_bits((uint16_t)(ve1 >> 16)));
         for (int hb = 0; hb < 2; hb++) {   // tiles longer than one entry per thread (rare)
             const int n = hb ? vc_n1 : vc_n0;
             const uint32_t* vt = a.vtile + (bhk * a.nblk + 2 * split + hb) * (int64_t)a.vtile_cap;
             for (int e = tid + 256; e < n; e += 256) {
                 const uint32_t ve = vt[e];
-                atomicAdd(&vsp[(ve >> 6) & 127u], s[64 * hb + (ve & 63u)] * h2f_bits((uint16_t)(ve >> 16)));
+                oadd(&vsp[(ve >> 6) & 127u], s[64 * hb + (ve & 63u)] * h2f_bits((uint16_t)(ve >> 16)));
             }
         }
     }
@@ -1078,7 +1116,7 @@ __global__ __launch_bounds__(256, NREP == 1 ? 5 : 1) void attn_decode_partial_sm
     if (tid < AD) {
         o = (op[0][tid] + op[1][tid]) + (op[2][tid] + op[3][tid]);
         if (a.rv) o += ot[0][tid] + ot[1][tid];
-        if (vtile_ok) o += vsp[tid];
+        if (vtile_ok) o += oget(vsp[tid]);
     }
     if (a.kv > 0 && !vtile_ok) {   // V outliers of the chunk's tokens that fall into this head's 128 columns, through the lists
         if (tid < AD) oacc[tid] = o;
@@ -1119,14 +1157,15 @@ __global__ __launch_bounds__(256, NREP == 1 ? 5 : 1) void attn_decode_partial_sm
                     if (cc[j] < c_hi) {
                         const int d = cc[j] - c_lo;
                         const float deq = fmaf(sc[j], (float)((word[j] >> (BITS * (d % CPW))) & MASK), mnv[j]);
-                        atomicAdd(&oacc[d], pt * (val[j] - deq));
+                        if constexpr (DET) osum_add(&vsp[d], pt * (val[j] - deq));           // (vsp: zero, no tile adds on this path)
+                        else atomicAdd(&oacc[d], pt * (val[j] - deq));
                     }
                 }
                 if (cc[3] >= c_hi) break;
             }
         }
         __syncthreads();
-        if (tid < AD) o = oacc[tid];
+        if (tid < AD) o = DET ? o + oget(vsp[tid]) : oacc[tid];
     }
     if (NREP == 1 && a.fold) __syncthreads();          // (sp / op are about to be reused by the merge)
     part_publish<NREP == 1>(a, bhq0 + r, split, o, m, l, &sp[0][0], &op[0][0]);
@@ -1249,9 +1288,9 @@ __global__ __launch_bounds__(256) void attn_decode_partial_mfma(AttnArgs a) {
     if (NREP == 1) {
         hkv = (int)div_sh(blockIdx.x, a.Hq / max(a.Hkv, 1), a.nrep_shift);
         bhq0 = (int64_t)b * a.Hq + blockIdx.x;
-    } else {
-        hkv = (int)blockIdx.x;
-        bhq0 = (int64_t)b * a.Hq + (int64_t)hkv * NREP;
+    } else {           // (shared-prefix launch: NREP consecutive rows of the sh_G * sh_S that share a KV head)
+        hkv = a.sh_S ? (int)((blockIdx.x * (uint32_t)NREP) / (uint32_t)(a.sh_G * a.sh_S)) : (int)blockIdx.x;
+        bhq0 = (int64_t)b * a.Hq + (int64_t)blockIdx.x * NREP;
     }
     const int64_t bhk = (int64_t)b * a.Hkv + hkv;
     const int t0 = split * SC;
@@ -1281,7 +1320,7 @@ __global__ __launch_bounds__(256) void attn_decode_partial_mfma(AttnArgs a) {
     const int seg_s0 = seg_at(t0), seg_s1 = seg_at(min(t0 + 64, t0 + tn - 1));
     uint16_t qb[NREP];
 #pragma unroll
-    for (int r = 0; r < NREP; r++) qb[r] = a.q[(bhq0 + r) * AD + dq];
+    for (int r = 0; r < NREP; r++) qb[r] = a.q[q_row(a, bhq0 + r) * AD + dq];
     const int wl = tid & (WPR - 1), rsub = tid / WPR;
     uint32_t kw[WPT], vw[WPT];
     {
@@ -1826,9 +1865,16 @@ int attn_decode_impl(const void* q, const void* kcode, const void* kscale, const
                                 int W, int ldk, int lsk, int tcap_v, int tf_k, int tf_v, int group, int bits, int mode,
                                 int rk, int rv, int kk, int kv, int seg0, int seglen, int wcap, const void* dyn_state,
                                 float qscale, void* out, void* lse, void* workspace, size_t workspace_bytes, void* stream,
-                     const void* kochunk, const void* vochunk, const StreamExtras* ex = nullptr, AttnArgs* keep = nullptr) {
-    // keep != nullptr (gear_attn_verify_cache): launch the partial kernel only -- no fold, no reduce -- and hand the launch's
-    // arguments (slot layout, where the window went) back to the caller, which merges the partials itself
+                     const void* kochunk, const void* vochunk, const StreamExtras* ex = nullptr, AttnArgs* keep = nullptr,
+                     int sh_S = 0, bool det = false) {
+    // det (gear_attn_decode_shared's two launches): the vector kernels' DET instantiations -- outlier terms as integer sums, so that
+    // the call's result does not depend on the order in which waves ran (the matrix-core kernel has no such sums to begin with)
+    // keep != nullptr (gear_attn_verify_cache, gear_attn_decode_shared): launch the partial kernel only -- no fold, no reduce -- and
+    // hand the launch's arguments (slot layout, where the window went) back to the caller, which merges the partials itself
+    // sh_S > 0 (gear_attn_decode_shared's prefix launch, with keep): B == 1 and Hq = sh_S * (the model's query heads), the rows of
+    // sh_S sequences over one stored prompt -- see AttnArgs::sh_S
+    GEAR_CHECK_ARG(sh_S == 0 || (keep && B == 1 && !dyn_state && Hq % sh_S == 0 && (Hq / sh_S) % Hkv == 0),
+                   "gear_attn_decode: bad shared-prefix launch");
     const int kk_stride = ex ? ex->kk_stride : 0, kk0 = ex ? ex->kk0 : 0, kkb = ex ? ex->kkb : 0, nbk_pitch = ex ? ex->nbk_pitch : 0;
     GEAR_CHECK_ARG(wcap >= W, "gear_attn_decode: window pitch %d smaller than the window %d", wcap, W);
     GEAR_CHECK_ARG(seglen == 0 || (seglen % 64 == 0 && seg0 % 64 == 0 && seg0 >= 0),
@@ -1856,6 +1902,7 @@ int attn_decode_impl(const void* q, const void* kcode, const void* kscale, const
     a.vcode = (const uint32_t*)vcode; a.vscale = vscale; a.vmn = vmn;
     a.vP = (const uint16_t*)vP; a.vQ = (const uint16_t*)vQ; a.voidx = (const uint16_t*)voidx; a.voval = (const uint16_t*)voval;
     a.B = B; a.Hq = Hq; a.Hkv = Hkv; a.T = T;
+    a.sh_S = sh_S; a.sh_G = sh_S ? Hq / sh_S / Hkv : 0;
     a.ldk = ldk; a.lsk = lsk; a.tcap_v = tcap_v; a.tf_k = tf_k; a.tf_v = tf_v;
     a.group = group; a.rk = (kP && kQ) ? rk : 0; a.rv = (vP && vQ) ? rv : 0;
     a.kk = (koidx && koval) ? kk : 0; a.kv = (voidx && voval) ? kv : 0;
@@ -1899,11 +1946,20 @@ int attn_decode_impl(const void* q, const void* kcode, const void* kscale, const
     // shapes once the launch has a workgroup per CU; slower for multi-head attention (one query head per KV head: the vector kernel's
     // work is not repeated there) and for a single KV head at batch 1.  attn_mfma: 0 = by that rule, 1 = whenever it applies,
     // -1 = never.
+    // Shared-prefix launch (sh_S > 0): n_rep = P rows share a KV head (query heads of the group x sequences); a workgroup takes the
+    // largest of 8 / 4 / 2 / 1 consecutive rows that divides P, P / nrep_m workgroups per (KV head, chunk).  The vector kernel
+    // reconstructs the chunk once per row, the matrix-core kernel once per workgroup: measured (7B layer, 4096-token prefix, DESIGN
+    // section 6 "Shared prefix") the grouping loses at 1 row (51 against 36 us) and by a little at 2 (48.0 against 46.6 us warm, 44.8
+    // against 42.6 cold) and wins from 4 rows on (50.7 against 60.2 us; 8: 56 against 92; 2 x 8: 92 against 158): SH_MF_MIN_ROWS = 4,
+    // once the launch fills the chip.
+    constexpr int SH_MF_MIN_ROWS = 4;
     const int n_rep = Hq / Hkv;
-    const int nrep_m = (n_rep == 2 || n_rep == 4 || n_rep == 8) ? n_rep : 1;
+    const int nrep_m = sh_S ? (n_rep % 8 == 0 ? 8 : n_rep % 4 == 0 ? 4 : n_rep % 2 == 0 ? 2 : 1)
+                            : ((n_rep == 2 || n_rep == 4 || n_rep == 8) ? n_rep : 1);
     const int mfo = gear_options().attn_mfma;
-    const bool mf_shape = small && group == 64 && mfo >= 0 && (a.kk == 0 || a.ktile) && (a.kv == 0 || a.vtile) &&
-                          (mfo > 0 || (nrep_m > 1 && (int64_t)B * Hkv * a.splits >= 256));
+    const bool mf_rule = sh_S ? (nrep_m >= SH_MF_MIN_ROWS && (int64_t)(Hq / nrep_m) * a.splits >= 256)
+                              : (nrep_m > 1 && (int64_t)B * Hkv * a.splits >= 256);
+    const bool mf_shape = small && group == 64 && mfo >= 0 && (a.kk == 0 || a.ktile) && (a.kv == 0 || a.vtile) && (mfo > 0 || mf_rule);
     // the fp16 window: one more chunk of the split on the vector short-chunk kernel (its own workgroup per query head in the same
     // launch; the reduce kernel then only merges) -- with every chunk of a head on one XCD this is the faster arrangement (one layer
     // at batch 1, caches rotated: 21.0 -> 20.0 us; 7B decode 326 -> 335 tok/s graph-replayed; before the XCD mapping it measured 1 us
@@ -1926,13 +1982,15 @@ int attn_decode_impl(const void* q, const void* kcode, const void* kscale, const
         // group's 2 / 4 / 8 query heads; default: one workgroup per query head (see common.h for the measurement)
         const int gq = gear_options().attn_gqa_group;
         const bool group_on = gq > 0 || (gq < 0 && (int64_t)B * Hq * a.splits >= 32768);
-        const int nrep_t = (small && group_on && (n_rep == 2 || n_rep == 4 || n_rep == 8)) ? n_rep : 1;
+        // (det: one row per workgroup -- the DET code exists for that instantiation only)
+        const int nrep_t = (small && group_on && !sh_S && !det && (n_rep == 2 || n_rep == 4 || n_rep == 8)) ? n_rep : 1;
         const dim3 gridg((unsigned)Hkv, a.pslots, (unsigned)B), grids((unsigned)Hq, a.pslots, (unsigned)B);
 #define GOS(BI, STT, RSV)                                                                                                  \
     do {                                                                                                                   \
         if (nrep_t == 8) hipLaunchKernelGGL((attn_decode_partial_small<BI, STT, RSV, 8>), gridg, dim3(256), 0, st, a);      \
         else if (nrep_t == 4) hipLaunchKernelGGL((attn_decode_partial_small<BI, STT, RSV, 4>), gridg, dim3(256), 0, st, a); \
         else if (nrep_t == 2) hipLaunchKernelGGL((attn_decode_partial_small<BI, STT, RSV, 2>), gridg, dim3(256), 0, st, a); \
+        else if (det) hipLaunchKernelGGL((attn_decode_partial_small<BI, STT, RSV, 1, true>), grids, dim3(256), 0, st, a);   \
         else hipLaunchKernelGGL((attn_decode_partial_small<BI, STT, RSV, 1>), grids, dim3(256), 0, st, a);                  \
     } while (0)
         const bool mf = mf_shape && a.pslots == a.splits;
@@ -1941,7 +1999,7 @@ int attn_decode_impl(const void* q, const void* kcode, const void* kscale, const
         fold_possible = !keep && small && !mf && nrep_t == 1 && !lse && (win_chunk || (W == 0 && !dyn_state)) && a.pslots <= RS_MAX_F &&
                         fold_wanted((int64_t)B * Hq * a.pslots);
         if (fold_possible && (a.arrive = fold_counters()) != nullptr) a.fold = 1;
-        const dim3 gridm((unsigned)(nrep_m > 1 ? Hkv : Hq), a.pslots, (unsigned)B);
+        const dim3 gridm((unsigned)(sh_S ? Hq / nrep_m : nrep_m > 1 ? Hkv : Hq), a.pslots, (unsigned)B);
 #define GOM(BI, STT, RSV)                                                                                                  \
     do {                                                                                                                   \
         if (nrep_m == 8) hipLaunchKernelGGL((attn_decode_partial_mfma<BI, STT, RSV, 8>), gridm, dim3(256), 0, st, a);       \
@@ -1957,6 +2015,7 @@ int attn_decode_impl(const void* q, const void* kcode, const void* kscale, const
         else if (small && r16) GOS(BI, STT, 16);                                                                \
         else if (small && r4) GOS(BI, STT, 4);                                                                  \
         else if (small) GOS(BI, STT, 8);                                                                        \
+        else if (det) hipLaunchKernelGGL((attn_decode_partial_kernel<BI, STT, true>), grid, dim3(256), 0, st, a); \
         else hipLaunchKernelGGL((attn_decode_partial_kernel<BI, STT>), grid, dim3(256), 0, st, a);              \
     } while (0)
         if (mode == 0) { if (bits == 2) GO(2, uint16_t); else GO(4, uint16_t); }
@@ -2427,5 +2486,186 @@ extern "C" int gear_attn_verify_cache(const gear_cache_view* c, const void* q, i
     m.lse = (float*)lse;
     hipLaunchKernelGGL(attn_verify_merge_kernel, dim3((unsigned)((int64_t)c->B * Hq * n)), dim3(256), 0, (hipStream_t)stream, m);
     GEAR_CHECK_LAUNCH("attn_verify_merge");
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// Shared-prefix decode: S sequences that continue ONE stored prompt (see include/gear_hip.h).  The prompt's compressed tokens live in
+// a batch-1 cache; the S * Hq query rows go over it through the decode partial dispatch as rows of its KV heads (as grouped-query
+// attention would: a chunk is read and reconstructed once per workgroup of up to 8 rows), every sequence's own compressed tokens go
+// through the ordinary dispatch over the batch-S tail cache, and one merge kernel per output row joins the prefix slots, the tail
+// slots and the tail's window rows in one fp32 softmax.  Three launches (two when the tails hold no compressed tokens yet).
+namespace {
+
+struct SharedMerge {
+    const uint16_t* q;                  // [S Hq, 128]
+    const float* po_p;                  // prefix slots, rows ordered [KV head][query head of the group][sequence]
+    const float* ml_p;
+    int pitch_p, ns_p;
+    const float* po_t;                  // tail slots, rows [S Hq]
+    const float* ml_t;
+    int pitch_t, ns_t;                  // (ns_t == 0: the tails hold no compressed tokens)
+    const uint16_t* kwin;               // [S Hkv, wcap, 128]
+    const uint16_t* vwin;
+    int Wm, wcap;                       // window rows scored here (0 when they rode along as a tail slot)
+    int S, Hq, Hkv;
+    float qscale;
+    uint16_t* out;                      // [S Hq, 128]
+    float* lse;                         // [S Hq] or null
+};
+
+// one output row x = (s, hq) per workgroup: scores of the Wm window rows (8 threads per key, 16 channels each), one fp32 softmax with
+// the (m, l) of the row's prefix and tail slots, then the weighted sum (two groups of 128 channel threads).  The arithmetic of
+// attn_verify_merge_kernel without chunk rows; a slot with m = -inf (an empty chunk) gets the coefficient 0.
+__global__ __launch_bounds__(256) void attn_shared_merge_kernel(SharedMerge v) {
+    __shared__ float qs[AD];
+    __shared__ float sc[128];
+    __shared__ float sml[2][2 * RS_MAX];
+    __shared__ float coef[2 * RS_MAX + 128];
+    __shared__ float og[2][AD];
+    __shared__ float stat[2];
+    const int tid = threadIdx.x;
+    const int64_t x = blockIdx.x;
+    const int sq = (int)(x / v.Hq), hq = (int)(x % v.Hq);
+    const int G = v.Hq / v.Hkv, hkv = hq / G;
+    const int64_t xp = ((int64_t)hkv * G + (hq - hkv * G)) * v.S + sq;      // the row of the prefix launch
+    const int64_t bhk = (int64_t)sq * v.Hkv + hkv;
+    const int ns = v.ns_p + v.ns_t, nk = v.Wm;
+    if (tid < AD) qs[tid] = h2f_bits(v.q[x * AD + tid]) * v.qscale;
+    if (tid < v.ns_p) {
+        sml[0][tid] = v.ml_p[(xp * v.pitch_p + tid) * 2];
+        sml[1][tid] = v.ml_p[(xp * v.pitch_p + tid) * 2 + 1];
+    } else if (tid < ns) {
+        sml[0][tid] = v.ml_t[(x * v.pitch_t + tid - v.ns_p) * 2];
+        sml[1][tid] = v.ml_t[(x * v.pitch_t + tid - v.ns_p) * 2 + 1];
+    }
+    __syncthreads();
+    const int kj = tid >> 3, part = tid & 7;
+    for (int k0 = 0; k0 < nk; k0 += 32) {                  // (block-uniform)
+        const int k = k0 + kj;
+        float acc = 0.0f;
+        if (k < nk) {
+            const uint4* kr4 = (const uint4*)(v.kwin + (bhk * v.wcap + k) * (int64_t)AD + part * 16);
+            float t[8];
+            unpack8(kr4[0], t);
+#pragma unroll
+            for (int c = 0; c < 8; c++) acc = fmaf(qs[part * 16 + c], t[c], acc);
+            unpack8(kr4[1], t);
+#pragma unroll
+            for (int c = 0; c < 8; c++) acc = fmaf(qs[part * 16 + 8 + c], t[c], acc);
+        }
+        acc += __shfl_xor(acc, 4, 64);
+        acc += __shfl_xor(acc, 2, 64);
+        acc += __shfl_xor(acc, 1, 64);
+        if (k < nk && part == 0) sc[k] = acc;
+    }
+    __syncthreads();
+    if (tid < 64) {   // statistics over <= 132 slots and <= 128 keys, strided over the 64 lanes of wave 0
+        float M = -INFINITY;
+        for (int s = tid; s < ns; s += 64) M = fmaxf(M, sml[0][s]);
+        for (int k = tid; k < nk; k += 64) M = fmaxf(M, sc[k]);
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) M = fmaxf(M, __shfl_xor(M, o, 64));
+        float Ls = 0.0f;
+        for (int s = tid; s < ns; s += 64) {
+            const float c = sml[0][s] == -INFINITY ? 0.0f : __expf(sml[0][s] - M);
+            coef[s] = c;
+            Ls = fmaf(c, sml[1][s], Ls);
+        }
+        for (int k = tid; k < nk; k += 64) {
+            const float c = __expf(sc[k] - M);
+            coef[2 * RS_MAX + k] = c;
+            Ls += c;
+        }
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) Ls += __shfl_xor(Ls, o, 64);
+        if (tid == 0) { stat[0] = M; stat[1] = Ls; }
+    }
+    __syncthreads();
+    const int grp = tid >> 7, d = tid & (AD - 1);
+    float o = 0.0f;
+    for (int s = grp; s < v.ns_p; s += 2) o = fmaf(coef[s], v.po_p[(xp * v.pitch_p + s) * AD + d], o);
+    for (int s = grp; s < v.ns_t; s += 2) o = fmaf(coef[v.ns_p + s], v.po_t[(x * v.pitch_t + s) * AD + d], o);
+    for (int k = grp; k < nk; k += 2) o = fmaf(coef[2 * RS_MAX + k], h2f_bits(v.vwin[(bhk * v.wcap + k) * (int64_t)AD + d]), o);
+    og[grp][d] = o;
+    __syncthreads();
+    if (tid < AD) {
+        v.out[x * AD + tid] = f2h_bits((og[0][tid] + og[1][tid]) / stat[1]);
+        if (v.lse && tid == 0) v.lse[x] = stat[0] + logf(stat[1]);
+    }
+}
+
+int view_kk(const gear_cache_view* c) { return (c->koidx && c->koval) ? (c->kkb == 0 ? c->kk0 : c->kk_cap) : 0; }
+
+}  // namespace
+
+extern "C" size_t gear_attn_decode_shared_workspace(int S, int Hq, int Tp, int T, int bits) {
+    if (S <= 0 || Hq <= 0 || Tp <= 0 || T < 0) return 0;
+    // the partial slots of the S Hq rows over the prefix, then those of the tail dispatch (each sized for its largest plan)
+    return gear_attn_decode_workspace(1, S * Hq, Tp, bits) + gear_attn_decode_workspace(S, Hq, T, bits);
+}
+
+extern "C" int gear_attn_decode_shared(const gear_cache_view* prefix, int Tp, const gear_cache_view* tail, int T, int W, const void* q,
+                                       int Hq, float qscale, void* out, void* lse, void* workspace, size_t workspace_bytes,
+                                       void* stream) {
+    GEAR_CHECK_ARG(prefix && tail, "gear_attn_decode_shared: null cache view");
+    GEAR_CHECK_ARG(prefix->B == 1, "gear_attn_decode_shared: the prefix view must have B == 1 (got %d)", prefix->B);
+    GEAR_CHECK_ARG(prefix->Hkv == tail->Hkv && prefix->D == tail->D && prefix->bits == tail->bits && prefix->group == tail->group &&
+                   prefix->mode == tail->mode && prefix->rk == tail->rk && prefix->rv == tail->rv,
+                   "gear_attn_decode_shared: prefix and tail views disagree (Hkv %d / %d, D %d / %d, bits %d / %d, group %d / %d, mode "
+                   "%d / %d, ranks %d,%d / %d,%d)", prefix->Hkv, tail->Hkv, prefix->D, tail->D, prefix->bits, tail->bits, prefix->group,
+                   tail->group, prefix->mode, tail->mode, prefix->rk, prefix->rv, tail->rk, tail->rv);
+    GEAR_CHECK_ARG(prefix->D == AD, "gear_attn_decode_shared: head_dim %d, must be 128", prefix->D);
+    const int S = tail->B, Hkv = tail->Hkv;
+    GEAR_CHECK_ARG(S > 0 && Hkv > 0, "gear_attn_decode_shared: S %d x Hkv %d", S, Hkv);
+    GEAR_CHECK_ARG(Tp > 0 && Tp % 64 == 0 && Tp <= prefix->tcap,
+                   "gear_attn_decode_shared: Tp = %d prefix tokens, must be a positive multiple of 64 within tcap = %d", Tp, prefix->tcap);
+    GEAR_CHECK_ARG(T >= 0 && T % 64 == 0 && T <= tail->tcap,
+                   "gear_attn_decode_shared: T = %d compressed tail tokens, must be a multiple of 64 in [0, tcap = %d]", T, tail->tcap);
+    GEAR_CHECK_ARG(W >= 0 && W <= tail->wcap && tail->wcap <= 128, "gear_attn_decode_shared: W = %d window tokens, the window holds "
+                   "wcap = %d (at most 128)", W, tail->wcap);
+    GEAR_CHECK_ARG(Hq > 0 && Hq % Hkv == 0, "gear_attn_decode_shared: Hq %d not a multiple of Hkv %d", Hq, Hkv);
+    GEAR_CHECK_ARG((int64_t)S * Hq <= 65535, "gear_attn_decode_shared: S %d x Hq %d query rows (at most 65535)", S, Hq);
+    const size_t need = gear_attn_decode_shared_workspace(S, Hq, Tp, T, tail->bits);
+    GEAR_CHECK_ARG(workspace && workspace_bytes >= need, "gear_attn_decode_shared: workspace of %zu bytes, needs %zu "
+                   "(gear_attn_decode_shared_workspace)", workspace_bytes, need);
+    GEAR_CHECK_ARG(q && out, "gear_attn_decode_shared: null q / out");
+    GEAR_CHECK_ARG(W == 0 || (tail->kwin && tail->vwin), "gear_attn_decode_shared: W > 0 needs the window tensors");
+    const size_t ws_p = gear_attn_decode_workspace(1, S * Hq, Tp, prefix->bits);
+    AttnArgs tmp, ap, at;
+    StreamExtras ex;
+    // 1. the prefix: S Hq rows over the batch-1 view, no window
+    view_to_args(prefix, tmp, ex);
+    const gear_cache_view* c = prefix;
+    int rc = attn_decode_impl(q, c->kcode, c->kscale, c->kmn, c->kP, c->kQ, c->koidx, c->koval, c->vcode, c->vscale, c->vmn, c->vP,
+                              c->vQ, c->voidx, c->voval, nullptr, nullptr, 1, S * Hq, Hkv, c->D, Tp, 0, c->ldk, c->lsk, c->tcap, c->tcap,
+                              c->tcap, c->group, c->bits, c->mode, c->rk, c->rv, view_kk(c), c->kv, c->seg0, c->seglen, 0, nullptr,
+                              qscale, out, nullptr, workspace, ws_p, stream, c->kochunk, c->vochunk, &ex, &ap, S, true);
+    if (rc != 0) return rc;
+    SharedMerge m;
+    m.po_p = ap.part_o; m.ml_p = ap.part_ml; m.pitch_p = ap.pslots; m.ns_p = ap.pslots;
+    m.po_t = m.ml_t = nullptr; m.pitch_t = 1; m.ns_t = 0;
+    m.Wm = W;
+    // 2. every sequence's own compressed tokens (+ its window, where the plan makes it a slot)
+    if (T > 0) {
+        c = tail;
+        view_to_args(c, tmp, ex);
+        rc = attn_decode_impl(q, c->kcode, c->kscale, c->kmn, c->kP, c->kQ, c->koidx, c->koval, c->vcode, c->vscale, c->vmn, c->vP, c->vQ,
+                              c->voidx, c->voval, c->kwin, c->vwin, S, Hq, Hkv, c->D, T, W, c->ldk, c->lsk, c->tcap, c->tcap, c->tcap,
+                              c->group, c->bits, c->mode, c->rk, c->rv, view_kk(c), c->kv, c->seg0, c->seglen, c->wcap, nullptr, qscale,
+                              out, nullptr, (char*)workspace + ws_p, workspace_bytes - ws_p, stream, c->kochunk, c->vochunk, &ex, &at, 0, true);
+        if (rc != 0) return rc;
+        m.po_t = at.part_o; m.ml_t = at.part_ml; m.pitch_t = at.pslots; m.ns_t = at.pslots;
+        if (at.pslots != at.splits) m.Wm = 0;                // the window rode along as the last slot
+    }
+    // 3. the merge
+    m.q = (const uint16_t*)q;
+    m.kwin = (const uint16_t*)tail->kwin; m.vwin = (const uint16_t*)tail->vwin; m.wcap = tail->wcap;
+    m.S = S; m.Hq = Hq; m.Hkv = Hkv;
+    m.qscale = qscale;
+    m.out = (uint16_t*)out;
+    m.lse = (float*)lse;
+    hipLaunchKernelGGL(attn_shared_merge_kernel, dim3((unsigned)((int64_t)S * Hq)), dim3(256), 0, (hipStream_t)stream, m);
+    GEAR_CHECK_LAUNCH("attn_shared_merge");
     return 0;
 }

@@ -21,7 +21,8 @@ from .sampling import sample_tokens
 
 class FastGearDecoder:
     def __init__(self, model, max_tokens: int, batch: int = 1, seed: int = 0, tp_rank: int = 0, tp_world: int = 1,
-                 tp_group=None, tp_exchange: str = "collective", v_selection: str = "exact", cache_kind: str = "gear"):
+                 tp_group=None, tp_exchange: str = "collective", v_selection: str = "exact", cache_kind: str = "gear",
+                 shared_prefix_tokens: int = 0):
         """tp_world > 1: the cache and the attention are sharded head-wise: this rank owns
         Hq / tp_world query heads with their KV heads -- local q/k/v projection rows, local compressed cache, local attention --
         and all-gathers the per-rank attention output (parallel.HeadGather, pre-allocated) in front of the replicated
@@ -36,7 +37,11 @@ class FastGearDecoder:
         compress call), "per_shard" = k / world inside the shard's own heads (rounds 1-3).
         cache_kind: "gear" (the compressed streaming cache) or "fp16" = cache.Fp16KVCache, the uncompressed baseline the reference's
         harness times beside the compressed models (cuda_supported_gear/test.py:41-62: model "None"): same weights, same fused GEMVs,
-        same attention split / merge kernels over fp16 rows; eager steps on one GPU only."""
+        same attention split / merge kernels over fp16 rows; eager steps on one GPU only.
+        shared_prefix_tokens > 0: shared-prefix decoding -- `batch` sequences continue ONE prompt.  A second cache pool with batch 1
+        and that capacity holds the prompt's compressed tokens once (same per-layer seeds: its payload is bit-identical to segment 0
+        of a plain batch-1 decoder); `max_tokens` then sizes only the per-sequence tails.  prefill_shared() fills both, step() then
+        attends through cache.attend_shared (gear_attn_decode_shared).  Eager steps on one GPU, compressed cache only."""
         self.model = model
         cfg = model.config
         self.cfg = cfg
@@ -60,6 +65,15 @@ class FastGearDecoder:
         if cache_kind == "fp16" and tp_world > 1:
             raise NotImplementedError("the fp16-cache baseline runs on one GPU")
         self.cache_kind = cache_kind
+        if shared_prefix_tokens < 0:
+            raise ValueError(f"shared_prefix_tokens = {shared_prefix_tokens}")
+        if shared_prefix_tokens and cache_kind == "fp16":
+            raise NotImplementedError("shared-prefix decoding is not implemented for the fp16-cache baseline (cache_kind='fp16')")
+        if shared_prefix_tokens and tp_world > 1:
+            raise NotImplementedError("shared-prefix decoding is not implemented for head-sharded decoders (tp_world > 1)")
+        self.shared_prefix_tokens = int(shared_prefix_tokens)
+        self.shared_live = False      # prefill_shared() ran: step() attends over the stored prompt + the per-sequence tails
+        self.prefix_pool = None
         tp = dict(rank=tp_rank, world=tp_world, group=tp_group, exact=v_selection == "exact") if tp_world > 1 else None
         self.pool = None if cache_kind == "fp16" else GearKVCachePool(len(model.model.layers), batch, self.Hkv, max_tokens, cc0, dev,
                                                                       self.D, seed=seed, heads_total=self.Hkv_full, tp=tp)
@@ -85,6 +99,12 @@ class FastGearDecoder:
                        GearKVCache(batch, self.Hkv, max_tokens, at.compress_config, dev, self.D, seed=seed + i,
                                    pool=self.pool, layer=i, heads_total=self.Hkv_full, tp=tp)),
                 rotary=at.rotary_emb))
+        if self.shared_prefix_tokens:
+            self.prefix_pool = GearKVCachePool(len(model.model.layers), 1, self.Hkv, self.shared_prefix_tokens, cc0, dev, self.D,
+                                               seed=seed, heads_total=self.Hkv_full)
+            for i, (lw, layer) in enumerate(zip(self.layers, model.model.layers)):
+                lw["prefix"] = GearKVCache(1, self.Hkv, self.shared_prefix_tokens, layer.self_attn.compress_config, dev, self.D,
+                                           seed=seed + i, pool=self.prefix_pool, layer=i, heads_total=self.Hkv_full)
         self.w_head = (model.lm_head.weight * model.model.norm.weight[None, :]).contiguous()
         self.pos = 0
         self.use_gemv = True
@@ -200,6 +220,46 @@ class FastGearDecoder:
     def prefill(self, input_ids: torch.Tensor) -> torch.Tensor:
         """Dense causal attention over the prompt (torch SDPA), compress each layer's K/V into its cache.
         Returns the logits of the last position [B, vocab]."""
+        return self._prefill(input_ids, False)
+
+    @torch.no_grad()
+    def prefill_shared(self, input_ids: torch.Tensor) -> torch.Tensor:
+        """Shared-prefix prefill: ONE prompt input_ids [1, T] for all `batch` sequences.  The dense prefill runs at batch 1; the first
+        T - T % residual tokens are compressed into the prefix caches (once), the T % residual remainder rows are copied into every
+        sequence's window -- the tails' block boundaries then fall on the same absolute positions as in an unshared decoder.
+        Returns the last position's logits repeated to [batch, vocab].  (A prompt shorter than `residual` has no compressed part:
+        the tails hold all of it and step() attends over them alone.)"""
+        if not self.shared_prefix_tokens:
+            raise ValueError("prefill_shared(): construct the decoder with shared_prefix_tokens > 0")
+        if input_ids.dim() != 2 or input_ids.shape[0] != 1 or input_ids.shape[1] < 1:
+            raise ValueError(f"prefill_shared(): input_ids must be [1, T >= 1] (one prompt for all sequences), got "
+                             f"{list(input_ids.shape)}")
+        pc = self.layers[0]["prefix"]
+        T = input_ids.shape[1]
+        if T - T % pc.R > pc.Tmax:
+            raise L.GearError(f"prefill_shared(): the prompt's compressed part ({T - T % pc.R} tokens) exceeds "
+                              f"shared_prefix_tokens = {self.shared_prefix_tokens} (capacity {pc.Tmax})")
+        return self._prefill(input_ids, True).repeat(self.batch, 1)       # (rows of their own: the sampler takes no stride-0 rows)
+
+    def _shared_refused(self, what):
+        if self.shared_live:
+            raise NotImplementedError(f"{what}: not implemented while a shared prefix is live (shared-prefix decoding has eager "
+                                      "step() / generate(shared_prefix=True) only)")
+
+    def _store_prompt_shared(self, lw, k, v):
+        """k, v [1, Hkv, T, 128] of the one prompt: compressed part -> the prefix cache, remainder rows -> every tail's window."""
+        pc, tc = lw["prefix"], lw["cache"]
+        assert tc.seq_len == 0
+        T = k.shape[2]
+        nq = T - T % pc.R
+        if nq:
+            pc.prefill(k[:, :, :nq], v[:, :, :nq])
+        tc.n_win = T - nq
+        if tc.n_win:
+            tc.kwin[:, :, :tc.n_win] = k[:, :, nq:]
+            tc.vwin[:, :, :tc.n_win] = v[:, :, nq:]
+
+    def _prefill(self, input_ids, shared):
         B, T = input_ids.shape
         m = self.model.model
         h = m.embed_tokens(input_ids)
@@ -217,7 +277,10 @@ class FastGearDecoder:
             cos, sin = lw["rotary"](v, pos)
             q, k = apply_rotary_pos_emb(q, k, cos, sin)
             k0 = self.tp_rank * self.Hkv
-            lw["cache"].prefill(k[:, k0:k0 + self.Hkv], v[:, k0:k0 + self.Hkv])
+            if shared:
+                self._store_prompt_shared(lw, k, v)
+            else:
+                lw["cache"].prefill(k[:, k0:k0 + self.Hkv], v[:, k0:k0 + self.Hkv])
             kk = k if n_rep == 1 else k.repeat_interleave(n_rep, 1)
             vv = v if n_rep == 1 else v.repeat_interleave(n_rep, 1)
             a = F.scaled_dot_product_attention(q, kk, vv, is_causal=True)
@@ -225,6 +288,7 @@ class FastGearDecoder:
             h = h + layer.mlp(layer.post_attention_layernorm(h))
         self.pos = T
         self._state_dirty = True
+        self.shared_live = bool(shared and self.layers[0]["prefix"].n_comp > 0)
         return self.model.lm_head(m.norm(h[:, -1]))
 
     # ------------------------------------------------------------------------------------------------ chunk extend
@@ -238,6 +302,7 @@ class FastGearDecoder:
         earlier ones as ordinary cache contents (compressed where a block boundary was crossed).  A call that would exceed the cache
         capacity is refused before anything changes."""
         from .cache import N_MAX_EXTEND, _check_room
+        self._shared_refused("extend()")
         if self.tp_world > 1:
             raise NotImplementedError("extend(): head-sharded (tp_world > 1) chunk extend is not implemented -- use step()")
         if torch.cuda.is_current_stream_capturing():
@@ -300,6 +365,7 @@ class FastGearDecoder:
         (the fused GEMVs while B n <= 4), RoPE at pos .. pos + n - 1 and per layer cache.attend_verify (the decode kernels).  Returns the logits of every position [B, n, vocab]; every
         layer's n post-RoPE K / V rows are kept until accept(m) commits rows 0 .. m - 1.  Changes no cache state."""
         from .cache import N_MAX_VERIFY, _check_room
+        self._shared_refused("verify()")
         if self.tp_world > 1:
             raise NotImplementedError("verify(): head-sharded (tp_world > 1) verification is not implemented -- use step()")
         if torch.cuda.is_current_stream_capturing():
@@ -344,6 +410,7 @@ class FastGearDecoder:
     def accept(self, m: int) -> int:
         """Commit rows 0 .. m - 1 (0 <= m <= n) of the last verify() to every layer's cache, exactly as extend() of those tokens
         commits them (the windows fill, the pooled block compressor runs at each boundary); advances pos.  Returns m."""
+        self._shared_refused("accept()")
         p = getattr(self, "_pending", None)
         if p is None or p["pos"] != self.pos:
             raise ValueError("accept(): no pending verify() (each verify() can be accepted once, before any other step)")
@@ -378,6 +445,8 @@ class FastGearDecoder:
         d_i (the bonus row draws from p): every emitted token is an exact sample from the filtered distribution.  a = the batch
         minimum of leading accepts; a row that accepted further emits its draft at a, a row rejected at a its residual draw."""
         from .speculative import accepted_lengths, ngram_draft
+        if self.shared_prefix_tokens:
+            raise NotImplementedError("generate_speculative(): not implemented for a shared-prefix decoder (shared_prefix_tokens > 0)")
         if draft == "ngram":
             drafter = ngram_draft
         elif callable(draft):
@@ -431,7 +500,7 @@ class FastGearDecoder:
         for lw in self.layers:
             cache = lw["cache"]
             q = self._norm_qkv_rope(res, lw, dyn=False)
-            a = cache.attend(q)
+            a = cache.attend_shared(q, lw["prefix"]) if self.shared_live else cache.attend(q)
             res = self._linear_add(self._attn_out(a), lw["wo"], res)
             act = self._norm_linear(res, lw["wgu"], swiglu=True)
             res = self._linear_add(act, lw["wd"], res)
@@ -482,6 +551,9 @@ class FastGearDecoder:
         return self._graph_step(token_ids, sampling)
 
     def _graph_step(self, token_ids, sampling):
+        if self.shared_prefix_tokens:
+            raise NotImplementedError("step_graph(): not implemented for a shared-prefix decoder (shared_prefix_tokens > 0): the "
+                                      "shared-prefix attention has eager steps only")
         if self.pool is None:
             raise NotImplementedError("step_graph(): the fp16-cache baseline has eager steps only")
         if self.gather is not None and not self.gather.capturable and not getattr(self, "_peer_tried", False):
@@ -541,13 +613,19 @@ class FastGearDecoder:
         return sample_tokens(logits, sampling, pos=self.pos)[0].view(-1, 1)
 
     @torch.no_grad()
-    def generate(self, input_ids: torch.Tensor, max_length: int, graph: bool = False, sampling=None) -> torch.Tensor:
+    def generate(self, input_ids: torch.Tensor, max_length: int, graph: bool = False, sampling=None,
+                 shared_prefix: bool = False) -> torch.Tensor:
         """Greedy decoding; with `sampling` (a sampling.SamplingParams) every token is drawn by gear_sample_tokens at its own
-        position -- the first from the prefill logits, the rest from step()'s (graph=True: step_graph_sampled(), same tokens)."""
+        position -- the first from the prefill logits, the rest from step()'s (graph=True: step_graph_sampled(), same tokens).
+        shared_prefix=True (a decoder built with shared_prefix_tokens > 0): input_ids is ONE prompt [1, T], the result is
+        [batch, max_length] -- `batch` continuations over the prompt stored once (prefill_shared()); the first token of every row
+        comes from the one prefill row, sampled with the row index as the sampler's sequence index."""
+        if shared_prefix and graph:
+            raise NotImplementedError("generate(shared_prefix=True, graph=True): shared-prefix decoding has eager steps only")
         if sampling is not None:
-            return self._generate_sampled(input_ids, max_length, graph, sampling)
-        logits = self.prefill(input_ids)
-        out = [input_ids]
+            return self._generate_sampled(input_ids, max_length, graph, sampling, shared_prefix)
+        logits = self.prefill_shared(input_ids) if shared_prefix else self.prefill(input_ids)
+        out = [input_ids.expand(self.batch, -1) if shared_prefix else input_ids]
         nxt = logits.argmax(-1, keepdim=True)
         out.append(nxt)
         if graph and sum(t.shape[1] for t in out) < max_length:
@@ -564,9 +642,9 @@ class FastGearDecoder:
         self.check_block_kernel()
         return torch.cat(out, dim=1)
 
-    def _generate_sampled(self, input_ids, max_length, graph, sampling):
-        logits = self.prefill(input_ids)
-        out = [input_ids]
+    def _generate_sampled(self, input_ids, max_length, graph, sampling, shared_prefix=False):
+        logits = self.prefill_shared(input_ids) if shared_prefix else self.prefill(input_ids)
+        out = [input_ids.expand(self.batch, -1) if shared_prefix else input_ids]
         nxt = self._sample(logits, sampling)
         out.append(nxt)
         if graph and sum(t.shape[1] for t in out) < max_length:

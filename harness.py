@@ -88,9 +88,20 @@ def run(variant, args, dev):
         sampling = SamplingParams(args.temperature, args.top_k, args.top_p, args.seed)
         hook_kw = dict(do_sample=True, temperature=args.temperature, top_k=args.top_k, top_p=args.top_p, seed=args.seed)
     fast_kw = {} if sampling is None else dict(sampling=sampling)
-    if variant == "gearl" and args.fast:
+    cache_bytes = None
+    if variant == "gearl" and args.fast and args.shared_prefix:
+        # the batch continues ONE prompt (row 0) stored once: a batch-1 prefix cache + per-sequence tails (gear_attn_decode_shared)
         from gear_amd.fast_decode import FastGearDecoder
-        out = FastGearDecoder(model, args.max_length + 8, batch=args.batch_size).generate(ids, args.max_length, **fast_kw)
+        dec = FastGearDecoder(model, args.max_length - args.prompt_len + args.residual + 8, batch=args.batch_size,
+                              shared_prefix_tokens=args.prompt_len)
+        out = dec.generate(ids[:1], args.max_length, shared_prefix=True, **fast_kw)
+        cache_bytes = sum(t.numel() * t.element_size() for pool in (dec.pool, dec.prefix_pool) for t in pool.buf.values())
+    elif variant == "gearl" and args.fast:
+        from gear_amd.fast_decode import FastGearDecoder
+        dec = FastGearDecoder(model, args.max_length + 8, batch=args.batch_size)
+        out = dec.generate(ids, args.max_length, **fast_kw)
+        cache_bytes = sum(t.numel() * t.element_size() for t in dec.pool.buf.values())
+        del dec
     elif variant == "None" and args.fast:
         # the control through the SAME decoder (fused GEMVs, gear_attn_decode_f16 over cache.Fp16KVCache): gearl and None then
         # differ in the cache only
@@ -104,11 +115,15 @@ def run(variant, args, dev):
     peak = torch.cuda.max_memory_allocated(dev) / 2 ** 20
     new = (out.shape[1] - args.prompt_len) * args.batch_size
     print(f"[{variant}{' (fast path)' if variant in ('gearl', 'None') and args.fast else ''}] Peak memory usage on GPU: {peak:.1f} MB")
+    if cache_bytes is not None:
+        print(f"[{variant}] allocated cache: {cache_bytes / 2 ** 20:.1f} MB{' (shared prefix)' if args.shared_prefix else ''}")
     print(f"[{variant}] time {dt:.3f}   ({new / dt:.1f} new tokens/s, batch {args.batch_size}, prompt {args.prompt_len} -> {out.shape[1]})")
     del model
     torch.cuda.empty_cache()
     return dict(variant=variant, fast=bool(args.fast and variant in ("gearl", "None")), batch_size=args.batch_size, prompt_len=args.prompt_len,
                 max_length=int(out.shape[1]), time_s=dt, new_tokens_per_s=new / dt, peak_mem_MiB=peak, layers=args.layers,
+                **(dict(cache_bytes=cache_bytes) if cache_bytes is not None else {}),
+                **(dict(shared_prefix=True) if args.shared_prefix and variant == "gearl" else {}),
                 **(dict(do_sample=True, temperature=args.temperature, top_k=args.top_k, top_p=args.top_p, seed=args.seed)
                    if args.do_sample else {}))
 
@@ -129,6 +144,8 @@ def main():
     ap.add_argument("--left", type=float, default=0.0, help="outlier fraction (fast path only: the hook's fused path stores none)")
     ap.add_argument("--layers", type=int, default=32)
     ap.add_argument("--fast", action="store_true", help="GEAR through FastGearDecoder (pre-allocated cache, fused kernels)")
+    ap.add_argument("--shared_prefix", action="store_true",
+                    help="with --fast: the batch continues ONE prompt stored once (shared-prefix decoding) instead of batch_size copies")
     ap.add_argument("--json", action="store_true")
     # sampling, with the defaults of GenerationBench/GenerationTest/evaluation_bbh_cot.py:381-390
     ap.add_argument("--do_sample", action="store_true", help="sample (temperature / top-k / top-p) instead of greedy decoding")
@@ -137,6 +154,8 @@ def main():
     ap.add_argument("--top_p", type=float, default=0.95)
     ap.add_argument("--seed", type=int, default=0, help="key of the sampler's random stream")
     args = ap.parse_args()
+    if args.shared_prefix and not args.fast:
+        raise SystemExit("--shared_prefix needs --fast (shared-prefix decoding lives in FastGearDecoder)")
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
     variants = ["gearl", "KIVI", "None"] if args.all else [v for v in ("gearl", "KIVI", "None") if v in args.model]

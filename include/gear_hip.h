@@ -413,6 +413,22 @@ size_t gear_attn_verify_workspace(int B, int Hq, int n, int T, int W);
 int gear_attn_verify_cache(const gear_cache_view* c, const void* q, int Hq, int n, int T, int W, const void* k_new,
                            const void* v_new, float qscale, void* out, void* lse, void* workspace, size_t workspace_bytes,
                            void* stream);
+/* ---- shared-prefix decode: S sequences over ONE stored prompt ----------------------------------------------------------------
+ * `prefix` is a view with B == 1 that holds the prompt's Tp compressed tokens (no window is read from it); `tail` is a view with
+ * B == S of the same configuration (Hkv, D, bits, group, mode, ranks) that holds what every sequence appended since: T compressed
+ * tokens and W window tokens each (all sequences advance in lockstep).  Output row (s, hq) is ONE fp32 softmax over the prefix's Tp
+ * tokens, then sequence s's T compressed tokens, then its W window rows.  The S Hq query rows go over the prefix through the decode
+ * partial dispatch as rows of its KV heads -- (Hq / Hkv) S rows share a KV head's chunks as a grouped-query group would; a
+ * workgroup serves 8 / 4 / 2 / 1 consecutive rows of them, q is addressed in place --, the tails go through the ordinary dispatch
+ * (skipped when T == 0), and one merge launch joins both sets of partial results with the window rows.  The attention options
+ * apply as for decode, except attn_fold.  No cache state changes.  The same call on the same data gives the same bits every time
+ * (sampled decoding with one seed repeats): the vector kernels run here with their outlier sums as integer sums.
+ *   Tp     positive multiple of 64, <= prefix->tcap;  T multiple of 64 in [0, tail->tcap];  0 <= W <= tail->wcap <= 128
+ *   q      fp16 [S, Hq, 128], Hq % Hkv == 0, S Hq <= 65535;  out fp16 [S, Hq, 128];  lse optional float [S, Hq]
+ *   workspace: gear_attn_decode_shared_workspace(S, Hq, Tp, T, bits) bytes.  Three launches (two when T == 0). */
+size_t gear_attn_decode_shared_workspace(int S, int Hq, int Tp, int T, int bits);
+int gear_attn_decode_shared(const gear_cache_view* prefix, int Tp, const gear_cache_view* tail, int T, int W, const void* q, int Hq,
+                            float qscale, void* out, void* lse, void* workspace, size_t workspace_bytes, void* stream);
 /* (Re)build the sparse tiles of K chunks [k_chunk0, k_chunk1) (128 tokens each) and V blocks [v_blk0, v_blk1) (64 tokens each) of a
  * cache that holds T compressed tokens: called after the prompt and after every appended block (the chunk the block lies in). */
 int gear_cache_tiles_build(const gear_cache_view* c, int T, int k_chunk0, int k_chunk1, int v_blk0, int v_blk1, void* stream);
