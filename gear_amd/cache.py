@@ -317,6 +317,43 @@ def _check_room(c, n):
                           "capacity exceeded")
 
 
+def _reorder_index(src_idx, B, dev):
+    """src_idx of a reorder call -> int32 device tensor [B].  A host list or CPU tensor is checked here (every entry in [0, B));
+    a device tensor is not read on the host -- gear_cache_reorder treats an entry outside [0, B) as identity."""
+    if isinstance(src_idx, torch.Tensor) and src_idx.is_cuda:
+        if src_idx.dtype not in (torch.int32, torch.int64) or tuple(src_idx.shape) != (B,):
+            raise ValueError(f"reorder: src_idx must be an int32 / int64 tensor [{B}], got {list(src_idx.shape)} {src_idx.dtype}")
+        return src_idx.to(torch.int32).contiguous()
+    if isinstance(src_idx, torch.Tensor):
+        if src_idx.dtype not in (torch.int32, torch.int64):
+            raise ValueError(f"reorder: src_idx must be an int32 / int64 tensor, got {src_idx.dtype}")
+        src_idx = src_idx.tolist()
+    idx = [int(i) for i in src_idx] if isinstance(src_idx, (list, tuple)) else None
+    if idx is None or len(idx) != B:
+        raise ValueError(f"reorder: src_idx must hold {B} sequence indices, got {src_idx!r}")
+    if any(i < 0 or i >= B for i in idx):
+        raise ValueError(f"reorder: src_idx {idx} has entries outside [0, {B})")
+    return torch.tensor(idx, dtype=torch.int32, device=dev)
+
+
+def _reorder(obj, bufs, d, n_layers, B, H, D, c0, src_idx):
+    """gear_cache_reorder over `bufs` ([n_layers * B, ...] storage) at the counters of cache c0; the view and the workspace are kept
+    on `obj`."""
+    lib = L.load()
+    dev = bufs["kwin"].device
+    idx = _reorder_index(src_idx, B, dev)
+    key = (c0.kk0, c0.seg0)
+    if getattr(obj, "_rview_key", None) != key:
+        obj._rview, obj._rview_key = _view(bufs, d, n_layers * B, H, D, c0.kk0, c0.seg0, kwin=True), key
+    view = obj._rview
+    wsb = lib.gear_cache_reorder_workspace(C_.byref(view), n_layers, B, c0.n_comp, c0.n_win)
+    if wsb and (obj._rws is None or obj._rws.numel() < wsb):
+        obj._rws = torch.empty((wsb,), dtype=torch.uint8, device=dev)
+    rc = lib.gear_cache_reorder(C_.byref(view), n_layers, B, c0.n_comp, c0.n_win, L.ptr(idx), L.ptr(obj._rws) if wsb else None,
+                                obj._rws.numel() if wsb else 0, L.stream_ptr(bufs["kwin"]))
+    L.check(rc, "gear_cache_reorder")
+
+
 class GearKVCachePool:
     """The buffers of ALL layers' caches as one tensor per field with a leading layer dimension.  Every layer's
     GearKVCache takes its (contiguous) slice, so nothing changes for the kernels; what the pool buys is the block boundary:
@@ -346,6 +383,16 @@ class GearKVCachePool:
         self.gen = torch.Generator(device=device)
         self.gen.manual_seed(seed)
         self.caches = []
+        self._rws = None
+
+    def reorder(self, src_idx):
+        """Beam-search gather along the batch axis, in place, of every layer at once (gear_cache_reorder, two launches): afterwards
+        sequence b holds in every layer what sequence src_idx[b] held -- compressed tokens, factors, outlier lists, tiles, window.
+        src_idx: int32 / int64 device tensor [batch] (read on the device, no synchronisation), a CPU tensor or a list (checked
+        here); repeats and cycles are allowed, sequences with src_idx[b] == b are not touched.  No counter changes."""
+        c0 = self.caches[0]
+        assert all(c.n_comp == c0.n_comp and c.n_win == c0.n_win and c.kk0 == c0.kk0 and c.seg0 == c0.seg0 for c in self.caches)
+        _reorder(self, self.buf, self.dims, self.L, self.B, self.H, self.D, c0, src_idx)
 
     def compress_all(self):
         """Every layer's window holds `residual` tokens: compress all of them in one go, in place behind the compressed
@@ -436,6 +483,7 @@ class GearKVCache:
         self._xws = None
         self._vws = None
         self._sws = None
+        self._rws = None
         self.use_tiles = True     # tests switch these off to compare the list paths
         self.use_chunk_index = True
         self._views = {}
@@ -629,6 +677,11 @@ class GearKVCache:
                                          L.stream_ptr(q))
         L.check(rc, "gear_attn_decode_shared")
         return (out, lse) if return_lse else out
+
+    def reorder(self, src_idx):
+        """GearKVCachePool.reorder for one cache (standalone, or one layer of a pool): sequence b takes over the state of sequence
+        src_idx[b], in place; n_comp / n_win / seg0 / kk0 do not change."""
+        _reorder(self, self.bufs, self.dims, 1, self.B, self.H, self.D, self, src_idx)
 
     def extend(self, k_new: torch.Tensor, v_new: torch.Tensor):
         """Commit n tokens (fp16 [B,Hkv,n,128], post-RoPE): through the window, compressing each time it holds `residual` tokens --

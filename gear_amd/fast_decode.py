@@ -511,6 +511,29 @@ class FastGearDecoder:
             self._after_boundary()
         return self._norm_linear(res, self.w_head)
 
+    # ------------------------------------------------------------------------------------------------ beam search
+    def reorder(self, src_idx):
+        """Sequence b continues from the history of sequence src_idx[b]: the per-sequence cache state of ALL layers is gathered along
+        the batch axis in place, in one call (GearKVCachePool.reorder -> gear_cache_reorder).  src_idx: int32 / int64 device tensor
+        [batch] (read on the device), a CPU tensor or a list.  With a shared prefix only the tails move -- the prefix pool is
+        untouched; on a plain decoder the whole cache moves, prompt segment included (correct, only expensive)."""
+        if self.tp_world > 1:
+            raise NotImplementedError("reorder(): not implemented for head-sharded decoders (tp_world > 1)")
+        if self.pool is None:
+            raise NotImplementedError("reorder(): not implemented for the fp16-cache baseline (cache_kind='fp16')")
+        self.pool.reorder(src_idx)
+        self._state_dirty = True
+
+    def generate_beam(self, input_ids: torch.Tensor, max_length: int, num_beams: int = None, eos_token_id: int = None,
+                      length_penalty: float = 1.0, num_return_sequences: int = 1, pad_token_id: int = 0):
+        """Beam search with `batch` beams over ONE prompt input_ids [1, T] (a decoder built with shared_prefix_tokens > 0;
+        num_beams, when given, must equal batch): prefill_shared() once, then per token log_softmax / top-2S in torch,
+        reorder(beam_idx) and step().  Returns (sequences [num_return_sequences, max_length] long, padded with pad_token_id, scores
+        [num_return_sequences] fp32: sum of log-probabilities / length ** length_penalty), best first.  The rule is fixed in
+        gear_amd/beam.py.  Eager steps only."""
+        from .beam import beam_search
+        return beam_search(self, input_ids, max_length, num_beams, eos_token_id, length_penalty, num_return_sequences, pad_token_id)
+
     # ------------------------------------------------------------------------------------------------ hipGraph decode
     def _sync_state(self):
         c = self.layers[0]["cache"]

@@ -92,9 +92,16 @@ def run(variant, args, dev):
     if variant == "gearl" and args.fast and args.shared_prefix:
         # the batch continues ONE prompt (row 0) stored once: a batch-1 prefix cache + per-sequence tails (gear_attn_decode_shared)
         from gear_amd.fast_decode import FastGearDecoder
-        dec = FastGearDecoder(model, args.max_length - args.prompt_len + args.residual + 8, batch=args.batch_size,
+        # --num_beams N: beam search with N beams over that prompt (generate_beam: one beam per sequence, the tails follow the
+        # beams through gear_cache_reorder); the reference's evaluation scripts hand num_beams to generate() the same way
+        bs = args.num_beams or args.batch_size
+        dec = FastGearDecoder(model, args.max_length - args.prompt_len + args.residual + 8, batch=bs,
                               shared_prefix_tokens=args.prompt_len)
-        out = dec.generate(ids[:1], args.max_length, shared_prefix=True, **fast_kw)
+        if args.num_beams:
+            out, beam_scores = dec.generate_beam(ids[:1], args.max_length, num_beams=bs, length_penalty=args.length_penalty,
+                                                 num_return_sequences=bs)
+        else:
+            out = dec.generate(ids[:1], args.max_length, shared_prefix=True, **fast_kw)
         cache_bytes = sum(t.numel() * t.element_size() for pool in (dec.pool, dec.prefix_pool) for t in pool.buf.values())
     elif variant == "gearl" and args.fast:
         from gear_amd.fast_decode import FastGearDecoder
@@ -113,17 +120,19 @@ def run(variant, args, dev):
     torch.cuda.synchronize()
     dt = time.time() - t0
     peak = torch.cuda.max_memory_allocated(dev) / 2 ** 20
-    new = (out.shape[1] - args.prompt_len) * args.batch_size
+    beams = args.num_beams if variant == "gearl" and args.num_beams else 0
+    new = (out.shape[1] - args.prompt_len) * (beams or args.batch_size)
     print(f"[{variant}{' (fast path)' if variant in ('gearl', 'None') and args.fast else ''}] Peak memory usage on GPU: {peak:.1f} MB")
     if cache_bytes is not None:
         print(f"[{variant}] allocated cache: {cache_bytes / 2 ** 20:.1f} MB{' (shared prefix)' if args.shared_prefix else ''}")
-    print(f"[{variant}] time {dt:.3f}   ({new / dt:.1f} new tokens/s, batch {args.batch_size}, prompt {args.prompt_len} -> {out.shape[1]})")
+    print(f"[{variant}] time {dt:.3f}   ({new / dt:.1f} new tokens/s, {f'{beams} beams' if beams else f'batch {args.batch_size}'}, prompt {args.prompt_len} -> {out.shape[1]})")
     del model
     torch.cuda.empty_cache()
     return dict(variant=variant, fast=bool(args.fast and variant in ("gearl", "None")), batch_size=args.batch_size, prompt_len=args.prompt_len,
                 max_length=int(out.shape[1]), time_s=dt, new_tokens_per_s=new / dt, peak_mem_MiB=peak, layers=args.layers,
                 **(dict(cache_bytes=cache_bytes) if cache_bytes is not None else {}),
                 **(dict(shared_prefix=True) if args.shared_prefix and variant == "gearl" else {}),
+                **(dict(num_beams=beams, length_penalty=args.length_penalty, best_score=float(beam_scores[0])) if beams else {}),
                 **(dict(do_sample=True, temperature=args.temperature, top_k=args.top_k, top_p=args.top_p, seed=args.seed)
                    if args.do_sample else {}))
 
@@ -146,6 +155,9 @@ def main():
     ap.add_argument("--fast", action="store_true", help="GEAR through FastGearDecoder (pre-allocated cache, fused kernels)")
     ap.add_argument("--shared_prefix", action="store_true",
                     help="with --fast: the batch continues ONE prompt stored once (shared-prefix decoding) instead of batch_size copies")
+    ap.add_argument("--num_beams", type=int, default=0,
+                    help="with --fast --shared_prefix: beam search with this many beams over the one prompt (generate_beam)")
+    ap.add_argument("--length_penalty", type=float, default=1.0, help="beam scores are divided by length ** length_penalty")
     ap.add_argument("--json", action="store_true")
     # sampling, with the defaults of GenerationBench/GenerationTest/evaluation_bbh_cot.py:381-390
     ap.add_argument("--do_sample", action="store_true", help="sample (temperature / top-k / top-p) instead of greedy decoding")
@@ -156,6 +168,12 @@ def main():
     args = ap.parse_args()
     if args.shared_prefix and not args.fast:
         raise SystemExit("--shared_prefix needs --fast (shared-prefix decoding lives in FastGearDecoder)")
+    if args.num_beams and not (args.fast and args.shared_prefix):
+        raise SystemExit("--num_beams needs --fast --shared_prefix (beam search runs over a shared prefix)")
+    if args.num_beams and args.do_sample:
+        raise SystemExit("--num_beams and --do_sample exclude each other (beam search is deterministic)")
+    if args.num_beams < 0:
+        raise SystemExit("--num_beams must be positive")
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
     variants = ["gearl", "KIVI", "None"] if args.all else [v for v in ("gearl", "KIVI", "None") if v in args.model]

@@ -429,6 +429,22 @@ int gear_attn_verify_cache(const gear_cache_view* c, const void* q, int Hq, int 
 size_t gear_attn_decode_shared_workspace(int S, int Hq, int Tp, int T, int bits);
 int gear_attn_decode_shared(const gear_cache_view* prefix, int Tp, const gear_cache_view* tail, int T, int W, const void* q, int Hq,
                             float qscale, void* out, void* lse, void* workspace, size_t workspace_bytes, void* stream);
+/* ---- beam search: gather the per-sequence state of a cache along its batch axis, in place ---------------------------------------
+ * After the call the live state of sequence b in every layer is what the live state of sequence src_idx[b] was before it, bit for
+ * bit, for every field the view has (the reference reorders its tuple cache through Hugging Face's _reorder_cache, one
+ * index_select per tensor; this cache is pre-allocated and pooled, so the gather runs in place over the live ranges only).
+ *   c        the pooled view with B = n_layers * batch (fields [n_layers, batch, ...]; kP / vP [n_layers, nseg, batch, ...]), or one
+ *            cache's view with n_layers = 1; the tensors behind the const pointers are WRITTEN
+ *   T, W     compressed tokens (multiple of 64, <= tcap) and window tokens (<= wcap) of every sequence: what is copied is codes /
+ *            scale / mn / token factors / V lists of the first T tokens, the first kk0 + kkb (T - seg0) / seglen entries of every K
+ *            list, the factor segments written so far, the tiles of the chunks / blocks that hold tokens, the first W window rows
+ *   src_idx  DEVICE int32 [batch], read on the device (no host synchronisation); repeats and cycles are allowed; a sequence with
+ *            src_idx[b] == b is not touched; an entry outside [0, batch) is treated as b
+ *   workspace: gear_cache_reorder_workspace(c, n_layers, batch, T, W) bytes (the live ranges of all sequences; 0 for an invalid
+ *            shape).  Two launches: sources -> workspace, workspace -> destinations (a destination may be another row's source). */
+size_t gear_cache_reorder_workspace(const gear_cache_view* c, int n_layers, int batch, int T, int W);
+int gear_cache_reorder(const gear_cache_view* c, int n_layers, int batch, int T, int W, const int32_t* src_idx, void* workspace,
+                       size_t workspace_bytes, void* stream);
 /* (Re)build the sparse tiles of K chunks [k_chunk0, k_chunk1) (128 tokens each) and V blocks [v_blk0, v_blk1) (64 tokens each) of a
  * cache that holds T compressed tokens: called after the prompt and after every appended block (the chunk the block lies in). */
 int gear_cache_tiles_build(const gear_cache_view* c, int T, int k_chunk0, int k_chunk1, int v_blk0, int v_blk1, void* stream);
