@@ -41,6 +41,8 @@ SIGNATURES = {
     "gear_attn_verify_cache": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, C.c_float, _vp, _vp, _vp, _sz, _vp]),
     "gear_attn_decode_shared_workspace": (_sz, [_i, _i, _i, _i, _i]),
     "gear_attn_decode_shared": (_i, [_vp, _i, _vp, _i, _i, _vp, _i, C.c_float, _vp, _vp, _vp, _sz, _vp]),
+    "gear_attn_extend_shared_workspace": (_sz, [_i, _i, _i, _i, _i, _i]),
+    "gear_attn_extend_shared": (_i, [_vp, _i, _vp, _i, _i, _vp, _i, _i, _vp, _vp, C.c_float, _vp, _vp, _vp, _sz, _vp]),
     "gear_cache_reorder_workspace": (_sz, [_vp, _i, _i, _i, _i]),
     "gear_cache_reorder": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "gear_outlier_chunk_index_ex": (_i, [_vp, _i64, _i64, _i64, _i64, _i, _i, _i, _i, _vp, _i, _vp]),

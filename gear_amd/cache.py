@@ -481,6 +481,7 @@ class GearKVCache:
         self.gen.manual_seed(seed)
         self._ws = None
         self._xws = None
+        self._xsws = None
         self._vws = None
         self._sws = None
         self._rws = None
@@ -676,6 +677,47 @@ class GearKVCache:
                                          Hq, 1.0 / math.sqrt(self.D), L.ptr(out), L.ptr(lse), L.ptr(self._sws), self._sws.numel(),
                                          L.stream_ptr(q))
         L.check(rc, "gear_attn_decode_shared")
+        return (out, lse) if return_lse else out
+
+    def attend_extend_shared(self, q: torch.Tensor, k_new: torch.Tensor, v_new: torch.Tensor, prefix: "GearKVCache",
+                             return_lse: bool = False):
+        """Shared-prefix chunk attention: attend_extend for the S sequences of this (tail) cache behind ONE stored prompt, `prefix`
+        (as for attend_shared: batch 1, an empty window, the same compress config).  q fp16 [S,Hq,n,128], k_new / v_new fp16
+        [S,Hkv,n,128] (post-RoPE) -> fp16 [S,Hq,n,128] (with return_lse also the fp32 [S,Hq,n] log-sum-exp): row (s, hq, i) is one
+        fp32 softmax over the prefix's tokens, sequence s's compressed tokens, its window and its chunk rows 0 .. i
+        (gear_attn_extend_shared).  Changes no state of either cache.  At most N_MAX_EXTEND tokens per call."""
+        if not isinstance(prefix, GearKVCache) or prefix.B != 1 or prefix.n_win != 0:
+            raise ValueError("attend_extend_shared: prefix must be a GearKVCache with batch 1 and an empty window")
+        if (prefix.H, prefix.D, prefix.bits, prefix.group, prefix.R, prefix.rk, prefix.rv, prefix.kv, prefix.kk_blk) != \
+                (self.H, self.D, self.bits, self.group, self.R, self.rk, self.rv, self.kv, self.kk_blk):
+            raise ValueError("attend_extend_shared: prefix and tail caches were built with different compress configs / head counts")
+        if q.dim() != 4:
+            raise ValueError(f"attend_extend_shared: q must be fp16 [{self.B}, Hq, n, {self.D}], got {list(q.shape)} {q.dtype}")
+        S, Hq, n = q.shape[0], q.shape[1], q.shape[2]
+        _check_rows(k_new, v_new, self.B, self.H, self.D, n)
+        if tuple(q.shape) != (self.B, Hq, n, self.D) or q.dtype != torch.float16:
+            raise ValueError(f"attend_extend_shared: q must be fp16 [{self.B}, Hq, {n}, {self.D}], got {list(q.shape)} {q.dtype}")
+        if n > N_MAX_EXTEND:
+            raise ValueError(f"attend_extend_shared: n = {n} query tokens, at most N_MAX_EXTEND = {N_MAX_EXTEND}")
+        lib = L.load()
+        q, k_new, v_new = q.contiguous(), k_new.contiguous(), v_new.contiguous()
+        L.require_gpu(q, k_new, v_new)
+        out = torch.empty_like(q)
+        lse = torch.empty((S, Hq, n), dtype=torch.float32, device=q.device) if return_lse else None
+        wsb = lib.gear_attn_extend_shared_workspace(S, Hq, n, max(prefix.n_comp, 64), self.n_comp, self.n_win)
+        if self._xsws is None or self._xsws.numel() < wsb:
+            self._xsws = torch.empty((wsb,), dtype=torch.uint8, device=q.device)
+        views = []
+        for c, win in ((prefix, False), (self, True)):
+            key = (c.kk0, c.seg0, win, True, True)
+            view = c._views.get(key)
+            if view is None:
+                view = c._views[key] = _view(c.bufs, c.dims, c.B, c.H, c.D, c.kk0, c.seg0, kwin=win)
+            views.append(view)
+        rc = lib.gear_attn_extend_shared(C_.byref(views[0]), prefix.n_comp, C_.byref(views[1]), self.n_comp, self.n_win, L.ptr(q), Hq,
+                                         n, L.ptr(k_new), L.ptr(v_new), 1.0 / math.sqrt(self.D), L.ptr(out), L.ptr(lse),
+                                         L.ptr(self._xsws), self._xsws.numel(), L.stream_ptr(q))
+        L.check(rc, "gear_attn_extend_shared")
         return (out, lse) if return_lse else out
 
     def reorder(self, src_idx):

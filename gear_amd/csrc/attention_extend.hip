@@ -16,6 +16,13 @@
 //   3. online softmax per row (fp32 running max / sum), P in fp16;
 //   4. O = alpha O + P V on v_mfma_f32_32x32x16_f16 (each wave two 32 x 32 blocks of the 64 x 128 output, in registers).
 // A second launch merges the splits' partial (o, m, l) per output row and normalises.
+//
+// Shared-prefix extend (gear_attn_extend_shared): S sequences behind ONE stored prompt.  The prefix pass is the same kernel with
+// PFX = true over the prefix view (B == 1): the batch is folded into the row axis -- M = S n G rows per KV head, row
+// m = (s n + i) G + gh, q addressed in place --, the keys are the Tp / 64 compressed pieces, nothing is masked.  A 64-row tile may
+// hold rows of several sequences: a prefix piece is read and dequantized once per 64 query rows of ANY sequences.  The tail pass is
+// the PFX = false kernel over the batch-S tail view (compressed tail pieces, window, chunk; tail-local causality), and
+// attn_extend_shared_merge joins both slot sets per output row (prefix splits first, then tail splits: a fixed order).
 #include <math.h>
 
 #include "common.h"
@@ -41,6 +48,7 @@ struct ExtArgs {
     int Hq, G, n, T, W;
     float qscale;
     int nmt, nsplit, pps, npc, np;
+    int S;                    // prefix pass only: sequences folded into the row axis
     int64_t kP_seg, vP_seg;   // elements between two factor segments
     float* part_o;            // [slots, 64, 128]
     float* part_ml;           // [slots, 64, 2]
@@ -68,6 +76,22 @@ int64_t ext_slots_bound(int B, int Hq, int n, int T, int W) {
     const int64_t nw = ((int64_t)B * Hq * n + 63) / 64 + (int64_t)B * Hq;
     const int64_t np = T / 64 + (W + n + 63) / 64;
     return std::min<int64_t>(X_TARGET_WG + nw, nw * np);
+}
+
+// the prefix pass of gear_attn_extend_shared: Hkv grid rows, S n G query rows each, the Tp / 64 compressed pieces only
+void ext_plan_prefix(int Hkv, int64_t rows, int Tp, ExtPlan& p) {
+    p.nmt = (int)((rows + 63) / 64);
+    p.npc = p.np = Tp / 64;
+    const int64_t nwork = (int64_t)Hkv * p.nmt;
+    const int64_t want = std::min<int64_t>(p.np, std::max<int64_t>(1, (X_TARGET_WG + nwork - 1) / nwork));
+    p.pps = (int)((p.np + want - 1) / want);
+    p.nsplit = (p.np + p.pps - 1) / p.pps;
+}
+
+// its slots for any Hkv dividing Hq: nwork = Hkv ceil(S n G / 64) <= S Hq n / 64 + Hq
+int64_t ext_prefix_slots_bound(int S, int Hq, int n, int Tp) {
+    const int64_t nw = ((int64_t)S * Hq * n + 63) / 64 + Hq;
+    return std::min<int64_t>(X_TARGET_WG + nw, nw * (Tp / 64));
 }
 
 __device__ __forceinline__ int x_lower_bound(const uint16_t* a, int n, int key) {
@@ -228,7 +252,10 @@ __device__ __forceinline__ void x_fill_f16(const ExtArgs& a, int64_t bh, int j0,
     }
 }
 
-template <int BITS>
+// PFX = false: one sequence per grid row (blockIdx.y = b * Hkv + hkv), rows m = i G + gh, causal over window + chunk.
+// PFX = true: the prefix pass of the shared call (blockIdx.y = hkv of the B == 1 view), rows m = (s n + i) G + gh of all S
+// sequences, compressed pieces only, no mask; padding rows (m >= S n G) carry q = 0 and are never merged.
+template <int BITS, bool PFX = false>
 __global__ __launch_bounds__(256) void attn_extend_partial(ExtArgs a) {
     __shared__ __align__(16) uint16_t qs[64 * XQP];
     __shared__ __align__(16) uint16_t kt[64 * XQP];
@@ -243,31 +270,42 @@ __global__ __launch_bounds__(256) void attn_extend_partial(ExtArgs a) {
     const int64_t bh = blockIdx.y;
     const int b = (int)(bh / a.c.Hkv), hkv = (int)(bh % a.c.Hkv);
     const int mt = blockIdx.x % a.nmt, split = blockIdx.x / a.nmt;
-    const int m0 = mt * 64, rows = a.n * a.G;
+    const int m0 = mt * 64, rows = PFX ? a.S * a.n * a.G : a.n * a.G;
     float* S = un;
 
     for (int it = tid; it < 64 * 16; it += 256) {
         const int r = it >> 4, c8 = it & 15, m = m0 + r;
         uint4 v = make_uint4(0, 0, 0, 0);
         if (m < rows) {
-            const int i = m / a.G, hq = hkv * a.G + m % a.G;
-            v = *(const uint4*)(a.q + (((int64_t)b * a.Hq + hq) * a.n + i) * XD + c8 * 8);
+            if constexpr (PFX) {
+                const int si = m / a.G, hq = hkv * a.G + m % a.G;            // si = s n + i
+                v = *(const uint4*)(a.q + (((int64_t)(si / a.n) * a.Hq + hq) * a.n + si % a.n) * XD + c8 * 8);
+            } else {
+                const int i = m / a.G, hq = hkv * a.G + m % a.G;
+                v = *(const uint4*)(a.q + (((int64_t)b * a.Hq + hq) * a.n + i) * XD + c8 * 8);
+            }
         }
         *(uint4*)(qs + r * XQP + c8 * 8) = v;
     }
     if (tid < 64) { sm[tid] = -INFINITY; sl[tid] = 0.0f; }
 
-    const int i_max = min(a.n - 1, (min(m0 + 63, rows - 1)) / a.G);
-    const int kend = a.T + a.W + i_max + 1;                  // keys [0, kend) can be visible to this tile
-    const int p_last = a.npc + (kend - a.T - 1) / 64;        // (kend > T always: every query sees itself)
-    const int p0 = split * a.pps, p1 = min(min(a.np, p0 + a.pps), p_last + 1);
+    const int p0 = split * a.pps;
+    int p1;
+    if constexpr (PFX) {
+        p1 = min(a.np, p0 + a.pps);                          // np == npc: every prefix piece is visible to every row
+    } else {
+        const int i_max = min(a.n - 1, (min(m0 + 63, rows - 1)) / a.G);
+        const int kend = a.T + a.W + i_max + 1;              // keys [0, kend) can be visible to this tile
+        const int p_last = a.npc + (kend - a.T - 1) / 64;    // (kend > T always: every query sees itself)
+        p1 = min(min(a.np, p0 + a.pps), p_last + 1);
+    }
     xf16 o0, o1;
 #pragma unroll
     for (int r = 0; r < 16; r++) { o0[r] = 0.0f; o1[r] = 0.0f; }
 
     for (int pc = p0; pc < p1; pc++) {
         __syncthreads();                                     // the previous piece's tiles are no longer read
-        const bool comp = pc < a.npc;
+        const bool comp = PFX || pc < a.npc;
         if (comp) x_fill_comp<BITS>(a, bh, b, hkv, pc * 64, kt, vt, un, (float*)ps);
         else x_fill_f16(a, bh, (pc - a.npc) * 64, kt, vt);
         __syncthreads();
@@ -287,9 +325,13 @@ __global__ __launch_bounds__(256) void attn_extend_partial(ExtArgs a) {
 #pragma unroll
             for (int r = 0; r < 16; r++) {
                 const int row = rb * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-                const int i = min((m0 + row) / a.G, a.n - 1);
-                const bool ok = kpos <= a.T + a.W + i;
-                S[row * XSP + key] = ok ? acc[r] * a.qscale : -INFINITY;
+                if constexpr (PFX) {
+                    S[row * XSP + key] = acc[r] * a.qscale;
+                } else {
+                    const int i = min((m0 + row) / a.G, a.n - 1);
+                    const bool ok = kpos <= a.T + a.W + i;
+                    S[row * XSP + key] = ok ? acc[r] * a.qscale : -INFINITY;
+                }
             }
         }
         __syncthreads();
@@ -388,6 +430,89 @@ __global__ __launch_bounds__(128) void attn_extend_merge(ExtArgs a) {
     if (a.lse && d == 0) a.lse[x] = M + logf(L);
 }
 
+struct ExtSharedMerge {
+    const float* po_p;        // prefix pass: [slots, 64, 128], [slots, 64, 2]
+    const float* pml_p;
+    const float* po_t;        // tail pass
+    const float* pml_t;
+    int nmt_p, nsplit_p, nmt_t, nsplit_t;
+    int Hq, Hkv, G, n;
+    uint16_t* out;            // [S, Hq, n, 128]
+    float* lse;               // [S, Hq, n] or null
+};
+
+// one output row (s, hq, i) per workgroup, one channel per thread: the prefix splits, then the tail splits (attn_extend_merge's
+// arithmetic; a split that saw no key has m = -inf and is skipped; the tail pass always holds the row's own chunk key, so L > 0)
+__global__ __launch_bounds__(128) void attn_extend_shared_merge(ExtSharedMerge a) {
+    const int64_t x = blockIdx.x;
+    const int i = (int)(x % a.n);
+    const int64_t shq = x / a.n;
+    const int s = (int)(shq / a.Hq), hq = (int)(shq % a.Hq);
+    const int hkv = hq / a.G, gh = hq % a.G;
+    const int64_t mp = ((int64_t)s * a.n + i) * a.G + gh;
+    const int mt = i * a.G + gh;
+    const int64_t base_p = ((int64_t)hkv * a.nmt_p + mp / 64) * a.nsplit_p;
+    const int64_t base_t = (((int64_t)s * a.Hkv + hkv) * a.nmt_t + mt / 64) * a.nsplit_t;
+    const int rp = (int)(mp % 64), rt = mt % 64, d = threadIdx.x;
+    float M = -INFINITY;
+    for (int k = 0; k < a.nsplit_p; k++) M = fmaxf(M, a.pml_p[((base_p + k) * 64 + rp) * 2]);
+    for (int k = 0; k < a.nsplit_t; k++) M = fmaxf(M, a.pml_t[((base_t + k) * 64 + rt) * 2]);
+    float L = 0.0f, acc = 0.0f;
+    for (int k = 0; k < a.nsplit_p; k++) {
+        const float ms = a.pml_p[((base_p + k) * 64 + rp) * 2];
+        if (ms == -INFINITY) continue;
+        const float e = __expf(ms - M);
+        L = fmaf(e, a.pml_p[((base_p + k) * 64 + rp) * 2 + 1], L);
+        acc = fmaf(e, a.po_p[((base_p + k) * 64 + rp) * XD + d], acc);
+    }
+    for (int k = 0; k < a.nsplit_t; k++) {
+        const float ms = a.pml_t[((base_t + k) * 64 + rt) * 2];
+        if (ms == -INFINITY) continue;
+        const float e = __expf(ms - M);
+        L = fmaf(e, a.pml_t[((base_t + k) * 64 + rt) * 2 + 1], L);
+        acc = fmaf(e, a.po_t[((base_t + k) * 64 + rt) * XD + d], acc);
+    }
+    a.out[x * XD + d] = f2h_bits(acc / L);
+    if (a.lse && d == 0) a.lse[x] = M + logf(L);
+}
+
+// the checks a view's compressed payload must pass before a kernel reads it (fn: the entry point's name in the message)
+int ext_check_payload(const gear_cache_view* c, const char* fn) {
+    GEAR_CHECK_ARG(c->bits == 2 || c->bits == 4, "%s: bits %d, must be 2 or 4", fn, c->bits);
+    GEAR_CHECK_ARG(c->group == 32 || c->group == 64, "%s: group %d, must be 32 or 64", fn, c->group);
+    GEAR_CHECK_ARG(c->mode == GEAR_MODE_FP16_STEPWISE, "%s: mode %d, the cache stores fp16 scales (mode 0)", fn, c->mode);
+    GEAR_CHECK_ARG(c->kcode && c->kscale && c->kmn && c->vcode && c->vscale && c->vmn, "%s: T > 0 needs the quantized payload", fn);
+    GEAR_CHECK_ARG(c->ldk * (32 / c->bits) >= c->tcap && c->lsk * c->group >= c->tcap,
+                   "%s: K row pitches ldk %d / lsk %d below the capacity %d", fn, c->ldk, c->lsk, c->tcap);
+    GEAR_CHECK_ARG(c->rk >= 0 && c->rk <= 16 && c->rv >= 0 && c->rv <= 16, "%s: rank %d / %d, at most 16", fn, c->rk, c->rv);
+    GEAR_CHECK_ARG((!c->kP || !c->rk || c->kQ) && (!c->vP || !c->rv || c->vQ), "%s: factor P without Q", fn);
+    GEAR_CHECK_ARG(!(c->koidx && (c->kk0 > 0 || c->kkb > 0)) || (c->koval && c->kk_cap >= c->kk0 && c->kk_cap > 0),
+                   "%s: K outlier lists (kk0 %d, kkb %d, kk_cap %d)", fn, c->kk0, c->kkb, c->kk_cap);
+    GEAR_CHECK_ARG(c->kkb == 0 || c->seglen % 64 == 0, "%s: segment length %d, must be a multiple of 64", fn, c->seglen);
+    GEAR_CHECK_ARG(c->seg0 % 64 == 0, "%s: seg0 %d, must be a multiple of 64", fn, c->seg0);
+    return 0;
+}
+
+// the launch arguments of one partial pass over view c (slots at part_o / part_ml follow from the plan)
+void ext_fill_args(ExtArgs& a, const gear_cache_view* c, bool comp, const void* q, const void* k_new, const void* v_new, int Hq, int n,
+                   int T, int W, float qscale, const ExtPlan& p, float* part_o, int64_t slots) {
+    a.c = *c;
+    if (!comp) { a.c.kP = a.c.vP = nullptr; }
+    a.q = (const uint16_t*)q;
+    a.knew = (const uint16_t*)k_new;
+    a.vnew = (const uint16_t*)v_new;
+    a.Hq = Hq; a.G = Hq / c->Hkv; a.n = n; a.T = T; a.W = W;
+    a.qscale = qscale;
+    a.nmt = p.nmt; a.nsplit = p.nsplit; a.pps = p.pps; a.npc = p.npc; a.np = p.np;
+    a.S = c->B;
+    a.kP_seg = (int64_t)c->B * c->Hkv * XD * c->rk;
+    a.vP_seg = (int64_t)c->B * c->Hkv * XD * c->rv;
+    a.part_o = part_o;
+    a.part_ml = part_o + slots * 64 * XD;
+    a.out = nullptr;
+    a.lse = nullptr;
+}
+
 }  // namespace
 
 extern "C" size_t gear_attn_extend_workspace(int B, int Hq, int n, int T, int W) {
@@ -409,24 +534,7 @@ extern "C" int gear_attn_extend_cache(const gear_cache_view* c, const void* q, i
     GEAR_CHECK_ARG((int64_t)T + W + n <= 65535, "gear_attn_extend_cache: T + W + n = %lld positions", (long long)T + W + n);
     GEAR_CHECK_ARG(q && k_new && v_new && out, "gear_attn_extend_cache: null q / k_new / v_new / out");
     GEAR_CHECK_ARG(W == 0 || (c->kwin && c->vwin), "gear_attn_extend_cache: W > 0 needs the window tensors");
-    if (T > 0) {
-        GEAR_CHECK_ARG(c->bits == 2 || c->bits == 4, "gear_attn_extend_cache: bits %d, must be 2 or 4", c->bits);
-        GEAR_CHECK_ARG(c->group == 32 || c->group == 64, "gear_attn_extend_cache: group %d, must be 32 or 64", c->group);
-        GEAR_CHECK_ARG(c->mode == GEAR_MODE_FP16_STEPWISE, "gear_attn_extend_cache: mode %d, the cache stores fp16 scales (mode 0)",
-                       c->mode);
-        GEAR_CHECK_ARG(c->kcode && c->kscale && c->kmn && c->vcode && c->vscale && c->vmn,
-                       "gear_attn_extend_cache: T > 0 needs the quantized payload");
-        GEAR_CHECK_ARG(c->ldk * (32 / c->bits) >= c->tcap && c->lsk * c->group >= c->tcap,
-                       "gear_attn_extend_cache: K row pitches ldk %d / lsk %d below the capacity %d", c->ldk, c->lsk, c->tcap);
-        GEAR_CHECK_ARG(c->rk >= 0 && c->rk <= 16 && c->rv >= 0 && c->rv <= 16, "gear_attn_extend_cache: rank %d / %d, at most 16",
-                       c->rk, c->rv);
-        GEAR_CHECK_ARG((!c->kP || !c->rk || c->kQ) && (!c->vP || !c->rv || c->vQ), "gear_attn_extend_cache: factor P without Q");
-        GEAR_CHECK_ARG(!(c->koidx && (c->kk0 > 0 || c->kkb > 0)) || (c->koval && c->kk_cap >= c->kk0 && c->kk_cap > 0),
-                       "gear_attn_extend_cache: K outlier lists (kk0 %d, kkb %d, kk_cap %d)", c->kk0, c->kkb, c->kk_cap);
-        GEAR_CHECK_ARG(c->kkb == 0 || c->seglen % 64 == 0, "gear_attn_extend_cache: segment length %d, must be a multiple of 64",
-                       c->seglen);
-        GEAR_CHECK_ARG(c->seg0 % 64 == 0, "gear_attn_extend_cache: seg0 %d, must be a multiple of 64", c->seg0);
-    }
+    if (T > 0 && ext_check_payload(c, "gear_attn_extend_cache")) return -1;
     ExtPlan p;
     ext_plan((int64_t)c->B * c->Hkv, Hq / c->Hkv, n, T, W, p);
     const int64_t slots = (int64_t)c->B * c->Hkv * p.nmt * p.nsplit;
@@ -434,19 +542,8 @@ extern "C" int gear_attn_extend_cache(const gear_cache_view* c, const void* q, i
     GEAR_CHECK_ARG(workspace && workspace_bytes >= need, "gear_attn_extend_cache: workspace of %zu bytes, needs %zu "
                    "(gear_attn_extend_workspace)", workspace_bytes, need);
     ExtArgs a;
-    a.c = *c;
-    if (T == 0) { a.c.kP = a.c.vP = nullptr; }
-    a.q = (const uint16_t*)q;
-    a.knew = (const uint16_t*)k_new;
-    a.vnew = (const uint16_t*)v_new;
-    a.Hq = Hq; a.G = Hq / c->Hkv; a.n = n; a.T = T; a.W = W;
-    a.qscale = qscale;
-    a.nmt = p.nmt; a.nsplit = p.nsplit; a.pps = p.pps; a.npc = p.npc; a.np = p.np;
-    a.kP_seg = (int64_t)c->B * c->Hkv * XD * c->rk;
-    a.vP_seg = (int64_t)c->B * c->Hkv * XD * c->rv;
-    uintptr_t base = ((uintptr_t)workspace + 255) & ~(uintptr_t)255;
-    a.part_o = (float*)base;
-    a.part_ml = a.part_o + slots * 64 * XD;
+    const uintptr_t base = ((uintptr_t)workspace + 255) & ~(uintptr_t)255;
+    ext_fill_args(a, c, T > 0, q, k_new, v_new, Hq, n, T, W, qscale, p, (float*)base, slots);
     a.out = (uint16_t*)out;
     a.lse = (float*)lse;
     hipStream_t st = (hipStream_t)stream;
@@ -456,5 +553,75 @@ extern "C" int gear_attn_extend_cache(const gear_cache_view* c, const void* q, i
     GEAR_CHECK_LAUNCH("attn_extend_partial");
     hipLaunchKernelGGL(attn_extend_merge, dim3((unsigned)((int64_t)c->B * Hq * n)), dim3(XD), 0, st, a);
     GEAR_CHECK_LAUNCH("attn_extend_merge");
+    return 0;
+}
+
+extern "C" size_t gear_attn_extend_shared_workspace(int S, int Hq, int n, int Tp, int T, int W) {
+    if (S <= 0 || Hq <= 0 || n <= 0 || Tp < 64 || T < 0 || W < 0) return 0;
+    return (size_t)(ext_prefix_slots_bound(S, Hq, n, Tp) + ext_slots_bound(S, Hq, n, T, W)) * 64 * (XD + 2) * sizeof(float) + 256;
+}
+
+extern "C" int gear_attn_extend_shared(const gear_cache_view* prefix, int Tp, const gear_cache_view* tail, int T, int W, const void* q,
+                                       int Hq, int n, const void* k_new, const void* v_new, float qscale, void* out, void* lse,
+                                       void* workspace, size_t workspace_bytes, void* stream) {
+    const char* fn = "gear_attn_extend_shared";
+    GEAR_CHECK_ARG(prefix && tail, "gear_attn_extend_shared: null cache view");
+    GEAR_CHECK_ARG(prefix->B == 1, "gear_attn_extend_shared: the prefix view must have B == 1 (got %d)", prefix->B);
+    GEAR_CHECK_ARG(prefix->Hkv == tail->Hkv && prefix->D == tail->D && prefix->bits == tail->bits && prefix->group == tail->group &&
+                       prefix->mode == tail->mode && prefix->rk == tail->rk && prefix->rv == tail->rv,
+                   "gear_attn_extend_shared: prefix and tail views disagree (Hkv %d / %d, D %d / %d, bits %d / %d, group %d / %d, mode "
+                   "%d / %d, ranks %d,%d / %d,%d)", prefix->Hkv, tail->Hkv, prefix->D, tail->D, prefix->bits, tail->bits, prefix->group,
+                   tail->group, prefix->mode, tail->mode, prefix->rk, prefix->rv, tail->rk, tail->rv);
+    GEAR_CHECK_ARG(prefix->D == XD, "gear_attn_extend_shared: head_dim %d, must be 128", prefix->D);
+    const int S = tail->B, Hkv = tail->Hkv;
+    GEAR_CHECK_ARG(S > 0 && Hkv > 0 && (int64_t)S * Hkv <= 65535, "gear_attn_extend_shared: S %d x Hkv %d (at most 65535)", S, Hkv);
+    GEAR_CHECK_ARG(n >= 1 && n <= X_NMAX, "gear_attn_extend_shared: n = %d query tokens, must be in [1, %d]", n, X_NMAX);
+    GEAR_CHECK_ARG(Tp > 0 && Tp % 64 == 0 && Tp <= prefix->tcap,
+                   "gear_attn_extend_shared: Tp = %d prefix tokens, must be a positive multiple of 64 within tcap = %d", Tp, prefix->tcap);
+    GEAR_CHECK_ARG(T >= 0 && T % 64 == 0 && T <= tail->tcap,
+                   "gear_attn_extend_shared: T = %d compressed tail tokens, must be a multiple of 64 in [0, tcap = %d]", T, tail->tcap);
+    GEAR_CHECK_ARG(W >= 0 && W <= tail->wcap, "gear_attn_extend_shared: W = %d window tokens, the window holds wcap = %d", W,
+                   tail->wcap);
+    GEAR_CHECK_ARG((int64_t)Tp + T + W + n <= 65535, "gear_attn_extend_shared: Tp + T + W + n = %lld positions (at most 65535)",
+                   (long long)Tp + T + W + n);
+    GEAR_CHECK_ARG(Hq > 0 && Hq % Hkv == 0, "gear_attn_extend_shared: Hq %d not a multiple of Hkv %d", Hq, Hkv);
+    GEAR_CHECK_ARG((int64_t)S * Hq * n <= 0x7FFFFF00, "gear_attn_extend_shared: S %d x Hq %d x n %d query rows (at most 2^31 - 256)", S,
+                   Hq, n);
+    GEAR_CHECK_ARG(q && k_new && v_new && out, "gear_attn_extend_shared: null q / k_new / v_new / out");
+    GEAR_CHECK_ARG(W == 0 || (tail->kwin && tail->vwin), "gear_attn_extend_shared: W > 0 needs the window tensors");
+    if (ext_check_payload(prefix, fn)) return -1;
+    if (T > 0 && ext_check_payload(tail, fn)) return -1;
+    const int G = Hq / Hkv;
+    ExtPlan pp, pt;
+    ext_plan_prefix(Hkv, (int64_t)S * n * G, Tp, pp);
+    ext_plan((int64_t)S * Hkv, G, n, T, W, pt);
+    const int64_t slots_p = (int64_t)Hkv * pp.nmt * pp.nsplit, slots_t = (int64_t)S * Hkv * pt.nmt * pt.nsplit;
+    GEAR_CHECK_ARG((int64_t)pp.nsplit * pp.nmt <= 0x7FFFFFFF, "gear_attn_extend_shared: %lld prefix workgroups per KV head",
+                   (long long)pp.nsplit * pp.nmt);
+    const size_t need = (size_t)(slots_p + slots_t) * 64 * (XD + 2) * sizeof(float) + 256;
+    GEAR_CHECK_ARG(workspace && workspace_bytes >= need, "gear_attn_extend_shared: workspace of %zu bytes, needs %zu "
+                   "(gear_attn_extend_shared_workspace)", workspace_bytes, need);
+    float* ws_p = (float*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+    float* ws_t = ws_p + slots_p * 64 * (XD + 2);
+    ExtArgs ap, at;
+    ext_fill_args(ap, prefix, true, q, k_new, v_new, Hq, n, Tp, 0, qscale, pp, ws_p, slots_p);
+    ap.S = S;
+    ext_fill_args(at, tail, T > 0, q, k_new, v_new, Hq, n, T, W, qscale, pt, ws_t, slots_t);
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid_p((unsigned)(pp.nsplit * pp.nmt), (unsigned)Hkv), grid_t((unsigned)(pt.nsplit * pt.nmt), (unsigned)(S * Hkv));
+    if (tail->bits == 4) hipLaunchKernelGGL((attn_extend_partial<4, true>), grid_p, dim3(256), 0, st, ap);
+    else hipLaunchKernelGGL((attn_extend_partial<2, true>), grid_p, dim3(256), 0, st, ap);
+    GEAR_CHECK_LAUNCH("attn_extend_partial (prefix)");
+    if (tail->bits == 4) hipLaunchKernelGGL((attn_extend_partial<4, false>), grid_t, dim3(256), 0, st, at);
+    else hipLaunchKernelGGL((attn_extend_partial<2, false>), grid_t, dim3(256), 0, st, at);
+    GEAR_CHECK_LAUNCH("attn_extend_partial (tail)");
+    ExtSharedMerge m;
+    m.po_p = ap.part_o; m.pml_p = ap.part_ml; m.po_t = at.part_o; m.pml_t = at.part_ml;
+    m.nmt_p = pp.nmt; m.nsplit_p = pp.nsplit; m.nmt_t = pt.nmt; m.nsplit_t = pt.nsplit;
+    m.Hq = Hq; m.Hkv = Hkv; m.G = G; m.n = n;
+    m.out = (uint16_t*)out;
+    m.lse = (float*)lse;
+    hipLaunchKernelGGL(attn_extend_shared_merge, dim3((unsigned)((int64_t)S * Hq * n)), dim3(XD), 0, st, m);
+    GEAR_CHECK_LAUNCH("attn_extend_shared_merge");
     return 0;
 }

@@ -41,7 +41,9 @@ class FastGearDecoder:
         shared_prefix_tokens > 0: shared-prefix decoding -- `batch` sequences continue ONE prompt.  A second cache pool with batch 1
         and that capacity holds the prompt's compressed tokens once (same per-layer seeds: its payload is bit-identical to segment 0
         of a plain batch-1 decoder); `max_tokens` then sizes only the per-sequence tails.  prefill_shared() fills both, step() then
-        attends through cache.attend_shared (gear_attn_decode_shared).  Eager steps on one GPU, compressed cache only."""
+        attends through cache.attend_shared (gear_attn_decode_shared).  Eager steps on one GPU, compressed cache only.
+        extend_shared() then feeds every sequence a chunk of its own behind the stored prompt (cache.attend_extend_shared), and
+        reset_shared() returns the tails to their state after prefill_shared(): one stored prompt serves batch after batch."""
         self.model = model
         cfg = model.config
         self.cfg = cfg
@@ -74,6 +76,7 @@ class FastGearDecoder:
         self.shared_prefix_tokens = int(shared_prefix_tokens)
         self.shared_live = False      # prefill_shared() ran: step() attends over the stored prompt + the per-sequence tails
         self.prefix_pool = None
+        self._shared_saved = None     # what reset_shared() restores: set by prefill_shared()
         tp = dict(rank=tp_rank, world=tp_world, group=tp_group, exact=v_selection == "exact") if tp_world > 1 else None
         self.pool = None if cache_kind == "fp16" else GearKVCachePool(len(model.model.layers), batch, self.Hkv, max_tokens, cc0, dev,
                                                                       self.D, seed=seed, heads_total=self.Hkv_full, tp=tp)
@@ -239,12 +242,39 @@ class FastGearDecoder:
         if T - T % pc.R > pc.Tmax:
             raise L.GearError(f"prefill_shared(): the prompt's compressed part ({T - T % pc.R} tokens) exceeds "
                               f"shared_prefix_tokens = {self.shared_prefix_tokens} (capacity {pc.Tmax})")
-        return self._prefill(input_ids, True).repeat(self.batch, 1)       # (rows of their own: the sampler takes no stride-0 rows)
+        logits = self._prefill(input_ids, True)
+        # reset_shared() goes back to exactly this point: position, the tails' generator states (the remainder rows are kept per
+        # layer by _store_prompt_shared); the ids and the logits row serve generate(reuse_prefix=True)
+        self._shared_saved = dict(ids=input_ids.clone(), logits=logits, pos=self.pos, pool_gen=self.pool.gen.get_state(),
+                                  gens=[lw["cache"].gen.get_state() for lw in self.layers])
+        return logits.repeat(self.batch, 1)       # (rows of their own: the sampler takes no stride-0 rows)
 
-    def _shared_refused(self, what):
+    def reset_shared(self):
+        """Return the decoder to its state right after prefill_shared() without touching the prefix pool: the tails are emptied
+        (n_comp = seg0 = kk0 = 0), the prompt's T % residual remainder rows go back into every tail window, pos and the generator
+        states of the tail pool and the per-layer tail caches are restored.  The stored prompt then serves the next batch: what
+        that batch computes is bit-identical to the same batch on a fresh decoder (every compressed block, its outlier lists and
+        its tiles are rewritten from position 0 on; nothing reads past the live counters)."""
+        sv = self._shared_saved
+        if sv is None:
+            raise ValueError("reset_shared(): run prefill_shared() first")
+        for lw, st in zip(self.layers, sv["gens"]):
+            tc = lw["cache"]
+            tc.n_comp = tc.seg0 = tc.kk0 = 0
+            k, v = lw["shared_rem"]
+            tc.n_win = k.shape[2]
+            if tc.n_win:
+                tc.kwin[:, :, :tc.n_win] = k
+                tc.vwin[:, :, :tc.n_win] = v
+            tc.gen.set_state(st)
+        self.pool.gen.set_state(sv["pool_gen"])
+        self.pos = sv["pos"]
+        self._state_dirty = True
+
+    def _shared_refused(self, what, hint=""):
         if self.shared_live:
             raise NotImplementedError(f"{what}: not implemented while a shared prefix is live (shared-prefix decoding has eager "
-                                      "step() / generate(shared_prefix=True) only)")
+                                      f"step() / extend_shared() / generate(shared_prefix=True) only){hint}")
 
     def _store_prompt_shared(self, lw, k, v):
         """k, v [1, Hkv, T, 128] of the one prompt: compressed part -> the prefix cache, remainder rows -> every tail's window."""
@@ -255,6 +285,7 @@ class FastGearDecoder:
         if nq:
             pc.prefill(k[:, :, :nq], v[:, :, :nq])
         tc.n_win = T - nq
+        lw["shared_rem"] = (k[:, :, nq:].clone(), v[:, :, nq:].clone())      # reset_shared() puts these few rows back
         if tc.n_win:
             tc.kwin[:, :, :tc.n_win] = k[:, :, nq:]
             tc.vwin[:, :, :tc.n_win] = v[:, :, nq:]
@@ -302,7 +333,7 @@ class FastGearDecoder:
         earlier ones as ordinary cache contents (compressed where a block boundary was crossed).  A call that would exceed the cache
         capacity is refused before anything changes."""
         from .cache import N_MAX_EXTEND, _check_room
-        self._shared_refused("extend()")
+        self._shared_refused("extend()", ": use extend_shared()")
         if self.tp_world > 1:
             raise NotImplementedError("extend(): head-sharded (tp_world > 1) chunk extend is not implemented -- use step()")
         if torch.cuda.is_current_stream_capturing():
@@ -317,6 +348,27 @@ class FastGearDecoder:
             _check_room(c0, n)
         elif c0.n_win + n > c0.R:
             raise L.GearError(f"extend(): {n} tokens after {c0.n_win} exceed the fp16 cache's capacity {c0.R}")
+        out = [self._extend_piece(input_ids[:, i:i + N_MAX_EXTEND]) for i in range(0, n, N_MAX_EXTEND)]
+        return out[0] if len(out) == 1 else torch.cat(out, 1)
+
+    @torch.no_grad()
+    def extend_shared(self, input_ids: torch.Tensor) -> torch.Tensor:
+        """extend() behind a shared prefix: after prefill_shared(), feed every sequence n tokens of its own, input_ids [batch, n]
+        (one n for all rows -- the sequences advance in lockstep; pad unequal messages to a common length).  Per layer the chunk
+        attention runs over the stored prompt, the sequence's tail and the chunk itself (cache.attend_extend_shared: a prompt piece
+        is reconstructed once per 64 query rows of any sequences, not once per decode step), then the tokens are committed to the
+        tails as n step() calls would commit them.  Returns the logits of every position [batch, n, vocab].  More than
+        N_MAX_EXTEND tokens go in committed pieces; a call that would exceed the tails' capacity is refused before anything
+        changes.  A prompt shorter than `residual` has no compressed part: the chunk then runs over the tails alone."""
+        from .cache import N_MAX_EXTEND, _check_room
+        if self._shared_saved is None:
+            raise ValueError("extend_shared(): run prefill_shared() first")
+        if torch.cuda.is_current_stream_capturing():
+            raise NotImplementedError("extend_shared(): chunk extend cannot be captured in a graph (host-side counters, block boundaries)")
+        if input_ids.dim() != 2 or input_ids.shape[0] != self.batch or input_ids.shape[1] < 1:
+            raise ValueError(f"extend_shared(): input_ids must be [{self.batch}, n >= 1], got {list(input_ids.shape)}")
+        n = input_ids.shape[1]
+        _check_room(self.layers[0]["cache"], n)
         out = [self._extend_piece(input_ids[:, i:i + N_MAX_EXTEND]) for i in range(0, n, N_MAX_EXTEND)]
         return out[0] if len(out) == 1 else torch.cat(out, 1)
 
@@ -336,7 +388,7 @@ class FastGearDecoder:
             cos, sin = lw["rotary"](v, pos)
             q, k = apply_rotary_pos_emb(q, k, cos, sin)
             q, k = q.contiguous(), k.contiguous()
-            a = lw["cache"].attend_extend(q, k, v)
+            a = lw["cache"].attend_extend_shared(q, k, v, lw["prefix"]) if self.shared_live else lw["cache"].attend_extend(q, k, v)
             ks.append(k)
             vs.append(v)
             h = h + F.linear(a.transpose(1, 2).reshape(B, n, Hq * D), lw["wo"])
@@ -637,18 +689,24 @@ class FastGearDecoder:
 
     @torch.no_grad()
     def generate(self, input_ids: torch.Tensor, max_length: int, graph: bool = False, sampling=None,
-                 shared_prefix: bool = False) -> torch.Tensor:
+                 shared_prefix: bool = False, suffix_ids: torch.Tensor = None, reuse_prefix: bool = False) -> torch.Tensor:
         """Greedy decoding; with `sampling` (a sampling.SamplingParams) every token is drawn by gear_sample_tokens at its own
         position -- the first from the prefill logits, the rest from step()'s (graph=True: step_graph_sampled(), same tokens).
         shared_prefix=True (a decoder built with shared_prefix_tokens > 0): input_ids is ONE prompt [1, T], the result is
         [batch, max_length] -- `batch` continuations over the prompt stored once (prefill_shared()); the first token of every row
-        comes from the one prefill row, sampled with the row index as the sampler's sequence index."""
+        comes from the one prefill row, sampled with the row index as the sampler's sequence index.
+        suffix_ids [batch, n] (with shared_prefix): every sequence's own message behind the shared prompt -- prefill_shared(),
+        then extend_shared(suffix_ids); the first token comes from the last extend row (sampler position T + n).  Rows of the
+        result are prompt | suffix_s | generated, and max_length counts all of it.
+        reuse_prefix=True (with shared_prefix): when a prompt is already stored, skip the prefill and reset_shared() instead --
+        input_ids must be the stored prompt (ValueError otherwise)."""
         if shared_prefix and graph:
             raise NotImplementedError("generate(shared_prefix=True, graph=True): shared-prefix decoding has eager steps only")
+        if (suffix_ids is not None or reuse_prefix) and not shared_prefix:
+            raise ValueError("generate(): suffix_ids / reuse_prefix need shared_prefix=True")
         if sampling is not None:
-            return self._generate_sampled(input_ids, max_length, graph, sampling, shared_prefix)
-        logits = self.prefill_shared(input_ids) if shared_prefix else self.prefill(input_ids)
-        out = [input_ids.expand(self.batch, -1) if shared_prefix else input_ids]
+            return self._generate_sampled(input_ids, max_length, graph, sampling, shared_prefix, suffix_ids, reuse_prefix)
+        logits, out = self._generate_start(input_ids, max_length, shared_prefix, suffix_ids, reuse_prefix)
         nxt = logits.argmax(-1, keepdim=True)
         out.append(nxt)
         if graph and sum(t.shape[1] for t in out) < max_length:
@@ -665,9 +723,29 @@ class FastGearDecoder:
         self.check_block_kernel()
         return torch.cat(out, dim=1)
 
-    def _generate_sampled(self, input_ids, max_length, graph, sampling, shared_prefix=False):
-        logits = self.prefill_shared(input_ids) if shared_prefix else self.prefill(input_ids)
-        out = [input_ids.expand(self.batch, -1) if shared_prefix else input_ids]
+    def _generate_start(self, input_ids, max_length, shared_prefix, suffix_ids, reuse_prefix):
+        """The prompt phase of generate(): (logits [B, vocab] the first token is taken from, the token columns so far)."""
+        if not shared_prefix:
+            return self.prefill(input_ids), [input_ids]
+        if suffix_ids is not None and (suffix_ids.dim() != 2 or input_ids.shape[1] + suffix_ids.shape[1] >= max_length):
+            raise ValueError(f"generate(): prompt ({input_ids.shape[1]}) + suffix {list(suffix_ids.shape)} leave no room for a "
+                             f"generated token within max_length = {max_length}")
+        sv = self._shared_saved
+        if reuse_prefix and sv is not None:
+            if input_ids.shape != sv["ids"].shape or not torch.equal(input_ids.to(sv["ids"].device), sv["ids"]):
+                raise ValueError("generate(reuse_prefix=True): input_ids is not the prompt stored by prefill_shared()")
+            self.reset_shared()
+            logits = sv["logits"].repeat(self.batch, 1)
+        else:
+            logits = self.prefill_shared(input_ids)
+        out = [input_ids.expand(self.batch, -1)]
+        if suffix_ids is not None:
+            logits = self.extend_shared(suffix_ids)[:, -1].contiguous()
+            out.append(suffix_ids)
+        return logits, out
+
+    def _generate_sampled(self, input_ids, max_length, graph, sampling, shared_prefix=False, suffix_ids=None, reuse_prefix=False):
+        logits, out = self._generate_start(input_ids, max_length, shared_prefix, suffix_ids, reuse_prefix)
         nxt = self._sample(logits, sampling)
         out.append(nxt)
         if graph and sum(t.shape[1] for t in out) < max_length:

@@ -429,6 +429,25 @@ int gear_attn_verify_cache(const gear_cache_view* c, const void* q, int Hq, int 
 size_t gear_attn_decode_shared_workspace(int S, int Hq, int Tp, int T, int bits);
 int gear_attn_decode_shared(const gear_cache_view* prefix, int Tp, const gear_cache_view* tail, int T, int W, const void* q, int Hq,
                             float qscale, void* out, void* lse, void* workspace, size_t workspace_bytes, void* stream);
+/* ---- shared-prefix extend: n tokens per sequence behind ONE stored prompt (system-prompt serving) -----------------------------
+ * gear_attn_extend_cache for S sequences that share a prompt: `prefix` (B == 1, Tp compressed tokens, its window is not read) and
+ * `tail` (B == S, same Hkv, D, bits, group, mode, ranks; T compressed + W window tokens per sequence, all in lockstep) as for
+ * gear_attn_decode_shared.  Output row (s, hq, i) is ONE fp32 softmax over the prefix's Tp tokens, then sequence s's T compressed
+ * tokens, then its W window rows, then its own chunk rows 0 .. i -- every term reconstructed as gear_attn_extend_cache does.  Three
+ * launches: the chunk kernel over the prefix with the batch folded into the row axis (S n Hq / Hkv rows per KV head, row
+ * (s n + i) (Hq / Hkv) + gh, q addressed in place, no mask: a 64-token prefix piece is read and dequantized once per 64 query rows
+ * of ANY sequences), the chunk kernel over the tail view (tail-local causality), and one merge of both sets of partial results.
+ * No cache state changes; no float atomics: the same call on the same data gives the same bits every time.
+ *   Tp     positive multiple of 64, <= prefix->tcap;  T multiple of 64 in [0, tail->tcap];  0 <= W <= tail->wcap
+ *   q      fp16 [S, Hq, n, 128]; k_new / v_new fp16 [S, Hkv, n, 128] (post-RoPE), 1 <= n <= 2048, Hq % Hkv == 0, S Hkv <= 65535,
+ *          Tp + T + W + n <= 65535
+ *   out    fp16 [S, Hq, n, 128]; lse optional float [S, Hq, n] (log-sum-exp of the scaled scores)
+ *   workspace: gear_attn_extend_shared_workspace(S, Hq, n, Tp, T, W) bytes: both passes' partial slots (bounds every Hkv that
+ *          divides Hq; 0 for an invalid shape). */
+size_t gear_attn_extend_shared_workspace(int S, int Hq, int n, int Tp, int T, int W);
+int gear_attn_extend_shared(const gear_cache_view* prefix, int Tp, const gear_cache_view* tail, int T, int W, const void* q, int Hq,
+                            int n, const void* k_new, const void* v_new, float qscale, void* out, void* lse, void* workspace,
+                            size_t workspace_bytes, void* stream);
 /* ---- beam search: gather the per-sequence state of a cache along its batch axis, in place ---------------------------------------
  * After the call the live state of sequence b in every layer is what the live state of sequence src_idx[b] was before it, bit for
  * bit, for every field the view has (the reference reorders its tuple cache through Hugging Face's _reorder_cache, one
