@@ -64,14 +64,35 @@ namespace {
 // phase clocks of k_select_kernel (measurement builds only: EXTRA=-DGEAR_KS_CLK; tools/exp_kselect_clk.py)
 #ifdef GEAR_KS_CLK
 __device__ unsigned long long ks_clk_buf[8 * 4096];
+__device__ unsigned int ks_todo_seen;      // lists the last launch handed to k_select_fix_kernel
 #define KS_CLK_AT(k) do { if (threadIdx.x == 0 && blockIdx.x < 4096) ks_clk_buf[blockIdx.x * 8 + (k)] = __builtin_readcyclecounter(); } while (0)
 #else
 #define KS_CLK_AT(k) do { } while (0)
 #endif
 
-constexpr int KS_CAP = 160;      // candidate slots per (channel, side) list
-constexpr int KS_STRIDE = 164;   // words between lists in LDS: 4 words of skew keep the quad-per-list reads conflict-free
+// Candidate slots per (channel, side) list = words between lists in LDS.  124 = 4 * 31: an odd number of 4-word steps, so the
+// quad-per-list reads of phase C.1 (16 lists x 4 lanes) touch 64 different banks.  With 124 slots the candidate area is 31 KB and
+// the workgroup, up to T = 4096 (8 KB of scratch), 39.5 KB + thr_lds: FOUR workgroups share a CU's 160 KB (160 slots: 49.5 KB,
+// three).  Beyond T = 4096 the scratch of phase C.2 grows with T (16 * T / 32 words) and three are resident again.  The host aims at
+// k + 5 sqrt(k) + 8 candidates (80 at k = 40); a list that collects more than KS_CAP is exact all the same -- it goes to
+// k_select_fix_kernel: 126 of the 262 144 lists of a launch on normal data at T = 4096, k = 40, against 8 with 160 slots (counted by
+// tools/exp_kselect_clk.py in a GEAR_KS_CLK build: profiles/kselect_tail_after.md).
+constexpr int KS_CAP = 124;
+constexpr int KS_STRIDE = KS_CAP;
+constexpr int KS_KPL = (KS_CAP + 31) / 32 * 8;   // keys per lane of a list's quad in phase C.1, in whole blocks of 8
+constexpr int KS_TARGET_MAX = 96;                // the host takes the candidate path while it aims at no more than this many
 constexpr int KS_B = 8;          // words per candidate batch
+static_assert(KS_STRIDE >= KS_CAP && (KS_STRIDE / 4) % 2 == 1 && KS_STRIDE % 4 == 0, "list stride: an odd number of 4-word steps");
+constexpr int KS_LR = (KS_CAP + 63) / 64;        // rounds in which a wave of phase C.2 reads a whole list (64 candidates each)
+static_assert(KS_CAP <= 4 * KS_KPL, "phase C.1 holds a list as KS_KPL keys per lane of its quad");
+// dynamic LDS of a workgroup in bytes: candidate lists + cnt + kthr + the scratch the three phases share
+constexpr size_t ks_lds_bytes(int T) {
+    const size_t nwords = (size_t)(T + 31) / 32;
+    const size_t a = 16 * 16 * 4, b = 256 * KS_B, c = 4 * 4 * nwords;
+    return ((size_t)64 * KS_STRIDE + 128 + (a > b ? (a > c ? a : c) : (b > c ? b : c))) * 4;
+}
+// four workgroups per CU up to T = 4096: 4 x (dynamic + the 128 bytes of thr_lds) within the CU's 160 KB
+static_assert(4 * (ks_lds_bytes(4096) + 128) <= 160 * 1024, "k_select_kernel: a fourth workgroup no longer fits into the CU's LDS");
 
 // sum over the 4 lanes of a DPP quad, result in all four (quad_perm xor 1, xor 2)
 __device__ __forceinline__ int quad_sum_i32(int v) {
@@ -270,8 +291,8 @@ __global__ __launch_bounds__(256) void k_select_kernel(SelArgs a) {
     // ---------------------------------------------------------------- phase C.1: the threshold of every list at once
     // One DPP quad per list (16 lists per wave, 64 per workgroup): lane i4 of the quad holds candidates i4, i4 + 4, ... as
     // composite keys (16-bit order key of the value, then 14 bits "earlier token first"), unique per list, and the quad finds
-    // the k-th largest by 31 rounds of bisection -- compare + add-with-carry per candidate, two DPP adds per round, no
-    // scalar dependency chain.  A list whose count is outside [k, KS_CAP] is left to the exact slow path below.
+    // the k-th largest in two stages (below: 16 bisection rounds on the value part, then the ties at the cut) -- a compare + add
+    // per candidate, two DPP adds per round, no scalar dependency chain.  A list whose count is outside [k, KS_CAP] is left to the exact slow path below.
     {
         const int L = 16 * wave + (lane >> 2), i4 = lane & 3, side = L & 1;
         const int n = (int)cnt[L];
@@ -280,9 +301,9 @@ __global__ __launch_bounds__(256) void k_select_kernel(SelArgs a) {
 #pragma unroll
         for (int d = 32; d >= 1; d >>= 1) jm = max(jm, __shfl_xor(jm, d, 64));
         jm = __builtin_amdgcn_readfirstlane(jm);                                   // candidates per lane, max over the wave
-        uint32_t key[KS_CAP / 4];
+        uint32_t key[KS_KPL];
 #pragma unroll
-        for (int j = 0; j < KS_CAP / 4; j++) {
+        for (int j = 0; j < KS_KPL; j++) {
             const int g = i4 + 4 * j;
             uint32_t c = 0u;
             if (fast && g < n) c = cand[L * KS_STRIDE + g];
@@ -295,7 +316,7 @@ __global__ __launch_bounds__(256) void k_select_kernel(SelArgs a) {
         auto count_ge = [&](uint32_t thr) __attribute__((always_inline)) {
             int c = 0;
 #pragma unroll
-            for (int blk = 0; blk < KS_CAP / 32; blk++) {
+            for (int blk = 0; blk < KS_KPL / 8; blk++) {
                 if (blk * 8 < jm) {
 #pragma unroll
                     for (int j = blk * 8; j < blk * 8 + 8; j++) c += (key[j] >= thr) ? 1 : 0;
@@ -331,7 +352,7 @@ __global__ __launch_bounds__(256) void k_select_kernel(SelArgs a) {
             for (int t = 0; t < nmax; t++) {
                 uint32_t m = 0u;
 #pragma unroll
-                for (int blk = 0; blk < KS_CAP / 32; blk++) {
+                for (int blk = 0; blk < KS_KPL / 8; blk++) {
                     if (blk * 8 < jm) {
 #pragma unroll
                         for (int j = blk * 8; j < blk * 8 + 8; j++) m = max(m, key[j] < bound ? key[j] : 0u);
@@ -365,8 +386,8 @@ __global__ __launch_bounds__(256) void k_select_kernel(SelArgs a) {
         __builtin_amdgcn_wave_barrier();
         // both sides of the channel move through the stages together (mark -> prefix -> emit): three LDS round trips per channel
         // instead of six, the two sides' loads and atomics in flight at the same time
-        uint32_t cv[2][3];                                            // candidate (bits << 16 | t)
-        bool sel[2][3], fast[2];
+        uint32_t cv[2][KS_LR];                                            // candidate (bits << 16 | t)
+        bool sel[2][KS_LR], fast[2];
 #pragma unroll
         for (int side = 0; side < 2; side++) {
             uint32_t* bm = side == 0 ? bmA : bmB;
@@ -375,7 +396,7 @@ __global__ __launch_bounds__(256) void k_select_kernel(SelArgs a) {
             const uint32_t kt = (uint32_t)__builtin_amdgcn_readfirstlane((int)kthr[list]);
             fast[side] = kt != 0u;
 #pragma unroll
-            for (int i = 0; i < 3; i++) {
+            for (int i = 0; i < KS_LR; i++) {
                 cv[side][i] = 0u;
                 sel[side][i] = false;
                 const int g = lane + 64 * i;
@@ -419,7 +440,7 @@ __global__ __launch_bounds__(256) void k_select_kernel(SelArgs a) {
             const uint32_t* pfx = side == 0 ? pfxA : pfxB;
             const int64_t lbase = ((bh * KD + ch) * 2 + (side == 0 ? 1 : 0)) * (int64_t)a.kcap + a.o_off;
 #pragma unroll
-            for (int i = 0; i < 3; i++) {
+            for (int i = 0; i < KS_LR; i++) {
                 if (sel[side][i]) {
                     const uint32_t t = cv[side][i] & 0xFFFFu;
                     const uint32_t r = pfx[t >> 5] + (uint32_t)__popc(bm[t >> 5] & ((1u << (t & 31u)) - 1u));
@@ -452,6 +473,9 @@ __global__ __launch_bounds__(256) void k_select_fix_kernel(SelArgs a) {
     __shared__ uint32_t fscan[4];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const uint32_t ntodo = *a.todo_cnt;
+#ifdef GEAR_KS_CLK
+    if (blockIdx.x == 0 && threadIdx.x == 0) ks_todo_seen = ntodo;
+#endif
     const int T = a.T, k = a.k, ntiles = (T + 63) >> 6;
     const int per = (T + 255) >> 8;                                   // tokens per thread in the ordered pass
     for (uint32_t w = blockIdx.x; w < ntodo; w += gridDim.x) {
@@ -1185,6 +1209,9 @@ void launch_main(const MainArgs& a, int64_t BH, bool fast, bool lr, bool tr, hip
 extern "C" int gear_debug_ks_clk(unsigned long long* out) {
     return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(ks_clk_buf), sizeof(unsigned long long) * 8 * 4096);
 }
+extern "C" int gear_debug_ks_todo(unsigned int* out) {
+    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(ks_todo_seen), sizeof(unsigned int));
+}
 #endif
 #ifdef GEAR_KF_CLK
 extern "C" int gear_debug_kf_clk(unsigned long long* out) {
@@ -1277,7 +1304,7 @@ extern "C" int gear_compress_key_fused(const void* x, int64_t BH, int T, int gro
         const double target = k + 5.0 * sqrt((double)k) + 8.0;
         double p = target / (double)T;
         if (p > 0.5) p = 0.5;
-        sa.zthr = (target > 0.6 * KS_CAP || (variant & 2) || gear_options().kselect_slow || one) ? 1e30f : (float)(-inv_norm_cdf(p));   // huge z: no candidates -> slow exact path
+        sa.zthr = (target > (double)KS_TARGET_MAX || (variant & 2) || gear_options().kselect_slow || one) ? 1e30f : (float)(-inv_norm_cdf(p));   // huge z: no candidates -> slow exact path
         sa.sstride = max(1, T / 1024);
         sa.rlen = 1.0f / (float)T;
         sa.obits = obits; sa.omean = omean; sa.oidx = (uint16_t*)oidx; sa.oval = (uint16_t*)oval;
@@ -1285,9 +1312,7 @@ extern "C" int gear_compress_key_fused(const void* x, int64_t BH, int T, int gro
         sa.todo_cnt = (uint32_t*)(base + ws.todo);
         sa.todo = sa.todo_cnt + 64;
         if (hipMemsetAsync(sa.todo_cnt, 0, 4, st) != hipSuccess) { gear_set_error("gear_compress_key_fused: memset failed"); return -2; }
-        const int nwords = (T + 31) / 32;
-        const size_t scr_words = (size_t)max(max(16 * 16 * 4, 256 * KS_B), 4 * 4 * nwords);
-        const size_t shmem = ((size_t)64 * KS_STRIDE + 128 + scr_words) * 4;
+        const size_t shmem = ks_lds_bytes(T);
         hipLaunchKernelGGL(k_select_kernel, dim3((unsigned)(4 * BH)), dim3(256), shmem, st, sa);
         GEAR_CHECK_LAUNCH("gear_compress_key_fused(select)");
         const unsigned fix_grid = (unsigned)(BH * 256 < 2048 ? BH * 256 : 2048);   // workgroups loop over the to-do list

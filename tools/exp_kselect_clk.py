@@ -14,6 +14,9 @@ torch.cuda.synchronize()
 buf = np.zeros((4096, 8), np.uint64)
 lib.gear_debug_ks_clk.argtypes = [ctypes.c_void_p]
 print("rc", lib.gear_debug_ks_clk(buf.ctypes.data))
+todo = np.zeros(1, np.uint32)
+lib.gear_debug_ks_todo.argtypes = [ctypes.c_void_p]
+print("rc", lib.gear_debug_ks_todo(todo.ctypes.data), "lists the last launch handed to k_select_fix_kernel: %d of %d" % (int(todo[0]), 32 * 32 * 256))
 t = buf.astype(np.float64)
 names = ["A: sample statistics + thresholds", "B: stream all tokens (wave 0)", "B: barrier", "row sums + mean", "C.1: thresholds of the lists (quad bisection)", "C.1: barrier", "C.2: outputs (8 channels per wave)"]
 life = t[:, 7] - t[:, 0]
@@ -21,4 +24,5 @@ print("lifetime median %.0f p10 %.0f p90 %.0f" % (np.median(life), np.percentile
 for i, n in enumerate(names):
     d = t[:, i + 1] - t[:, i]
     print("  %-48s median %8.0f  p90 %8.0f" % (n, np.median(d), np.percentile(d, 90)))
-print("launch span %.0f cycles; workgroups resident at once ~ %.0f" % (t[:, 7].max() - t[:, 0].min(), life.sum() / (t[:, 7].max() - t[:, 0].min())))
+span = t[:, 7].max() - t[:, 0].min()
+print("launch span %.0f cycles; workgroups resident at once ~ %.0f (%.2f per CU of 256)" % (span, life.sum() / span, life.sum() / span / 256))
