@@ -45,6 +45,9 @@ SIGNATURES = {
     "gear_attn_extend_shared": (_i, [_vp, _i, _vp, _i, _i, _vp, _i, _i, _vp, _vp, C.c_float, _vp, _vp, _vp, _sz, _vp]),
     "gear_cache_reorder_workspace": (_sz, [_vp, _i, _i, _i, _i]),
     "gear_cache_reorder": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    "gear_cache_snapshot_bytes": (_sz, [_vp, _i, _i, _i, _i, _i]),
+    "gear_cache_snapshot": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
+    "gear_cache_restore": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _sz, _i, _vp]),
     "gear_outlier_chunk_index_ex": (_i, [_vp, _i64, _i64, _i64, _i64, _i, _i, _i, _i, _vp, _i, _vp]),
     "gear_quant_rows_whole": (_i, [_vp, _i64, _i, _i64, _i64, _i, _i, _i64, _i, _i, _vp, _i, _vp, _vp, _vp]),
     "gear_quant_rows_ragged": (_i, [_vp, _i64, _i, _i64, _i64, _i, _i, _i64, _i, _i, _i, _i, _vp, _vp, _vp]),

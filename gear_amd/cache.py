@@ -336,16 +336,22 @@ def _reorder_index(src_idx, B, dev):
     return torch.tensor(idx, dtype=torch.int32, device=dev)
 
 
+def _state_view(obj, bufs, d, NB, H, D, kk0, seg0):
+    """The window-carrying view of `bufs` at (kk0, seg0), kept on `obj`: what gear_cache_reorder and the snapshot entry points walk
+    (the live ranges and the snapshot blob's layout depend on both counters)."""
+    key = (kk0, seg0)
+    if obj._rview_key != key:
+        obj._rview, obj._rview_key = _view(bufs, d, NB, H, D, kk0, seg0, kwin=True), key
+    return obj._rview
+
+
 def _reorder(obj, bufs, d, n_layers, B, H, D, c0, src_idx):
     """gear_cache_reorder over `bufs` ([n_layers * B, ...] storage) at the counters of cache c0; the view and the workspace are kept
     on `obj`."""
     lib = L.load()
     dev = bufs["kwin"].device
     idx = _reorder_index(src_idx, B, dev)
-    key = (c0.kk0, c0.seg0)
-    if getattr(obj, "_rview_key", None) != key:
-        obj._rview, obj._rview_key = _view(bufs, d, n_layers * B, H, D, c0.kk0, c0.seg0, kwin=True), key
-    view = obj._rview
+    view = _state_view(obj, bufs, d, n_layers * B, H, D, c0.kk0, c0.seg0)
     wsb = lib.gear_cache_reorder_workspace(C_.byref(view), n_layers, B, c0.n_comp, c0.n_win)
     if wsb and (obj._rws is None or obj._rws.numel() < wsb):
         obj._rws = torch.empty((wsb,), dtype=torch.uint8, device=dev)
@@ -384,6 +390,7 @@ class GearKVCachePool:
         self.gen.manual_seed(seed)
         self.caches = []
         self._rws = None
+        self._rview = self._rview_key = None
 
     def reorder(self, src_idx):
         """Beam-search gather along the batch axis, in place, of every layer at once (gear_cache_reorder, two launches): afterwards
@@ -393,6 +400,27 @@ class GearKVCachePool:
         c0 = self.caches[0]
         assert all(c.n_comp == c0.n_comp and c.n_win == c0.n_win and c.kk0 == c0.kk0 and c.seg0 == c0.seg0 for c in self.caches)
         _reorder(self, self.buf, self.dims, self.L, self.B, self.H, self.D, c0, src_idx)
+
+    def snapshot(self, seq=None):
+        """The live state of every layer as one packed blob (snapshot.CacheSnapshot; gear_cache_snapshot, one launch over the live
+        bytes): all sequences with the counters and the generator states of the pool and of every layer's cache (seq=None), or
+        sequence `seq` alone (no generator states: they belong to the whole batch)."""
+        from . import snapshot as S
+        return S.take(self, self.buf, self.dims, self.L, self.B, self.H, self.D, self.caches, self.gen, seq)
+
+    def restore(self, snap, seq=None):
+        """Put a snapshot back (gear_cache_restore, one launch).  A whole-batch snapshot of this batch size with seq=None restores
+        everything -- buffers, every cache's counters, the generator states: what follows is bit-identical to what followed the
+        snapshot.  A one-sequence snapshot with seq=None is broadcast to every sequence and sets the counters (one stored history
+        forked `batch` ways); with seq=b it writes slot b alone and its counters must equal the current ones (the sequences of a
+        pool advance in lockstep; ValueError otherwise).  In both one-sequence modes the generators are left alone: they draw the
+        start bases of all batch rows at once, so later blocks of a fork follow the destination's generator.  A whole snapshot of
+        a batch-1 standalone cache (which carries no pool generator state) counts as a one-sequence snapshot here.
+        Refused before anything changes: a geometry that differs from this pool's (ValueError naming the entry), more tokens
+        than the capacity (GearError).  Nothing is cleared past the live ranges: every block, list and tile is rewritten from
+        the counters on and nothing reads past them (the argument DESIGN.md "Shared-prefix extend" gives for reset_shared())."""
+        from . import snapshot as S
+        S.put(self, self.buf, self.dims, self.L, self.B, self.H, self.D, self.caches, self.gen, snap, seq)
 
     def compress_all(self):
         """Every layer's window holds `residual` tokens: compress all of them in one go, in place behind the compressed
@@ -485,6 +513,7 @@ class GearKVCache:
         self._vws = None
         self._sws = None
         self._rws = None
+        self._rview = self._rview_key = None
         self.use_tiles = True     # tests switch these off to compare the list paths
         self.use_chunk_index = True
         self._views = {}
@@ -724,6 +753,19 @@ class GearKVCache:
         """GearKVCachePool.reorder for one cache (standalone, or one layer of a pool): sequence b takes over the state of sequence
         src_idx[b], in place; n_comp / n_win / seg0 / kk0 do not change."""
         _reorder(self, self.bufs, self.dims, 1, self.B, self.H, self.D, self, src_idx)
+
+    def snapshot(self, seq=None):
+        """GearKVCachePool.snapshot for one cache (standalone, or one layer of a pool): the live state as one packed blob, all
+        sequences with the counters and this cache's generator state (seq=None) or one sequence."""
+        from . import snapshot as S
+        return S.take(self, self.bufs, self.dims, 1, self.B, self.H, self.D, [self], None, seq)
+
+    def restore(self, snap, seq=None):
+        """GearKVCachePool.restore for one cache: whole batch (counters and generator state included), a one-sequence snapshot
+        broadcast to every sequence (seq=None) or into slot `seq` at equal counters; the same refusals, the same reliance on
+        nothing reading past the live counters."""
+        from . import snapshot as S
+        S.put(self, self.bufs, self.dims, 1, self.B, self.H, self.D, [self], None, snap, seq)
 
     def extend(self, k_new: torch.Tensor, v_new: torch.Tensor):
         """Commit n tokens (fp16 [B,Hkv,n,128], post-RoPE): through the window, compressing each time it holds `residual` tokens --

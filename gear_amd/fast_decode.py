@@ -576,6 +576,91 @@ class FastGearDecoder:
         self.pool.reorder(src_idx)
         self._state_dirty = True
 
+    # ------------------------------------------------------------------------------------------------ snapshots
+    def _snapshot_refused(self, what):
+        if self.tp_world > 1:
+            raise NotImplementedError(f"{what}: not implemented for head-sharded decoders (tp_world > 1)")
+        if self.pool is None:
+            raise NotImplementedError(f"{what}: not implemented for the fp16-cache baseline (cache_kind='fp16')")
+
+    def _prefix_parts(self):
+        sv = self._shared_saved
+        saved = dict(ids=sv["ids"].clone(), logits=sv["logits"].clone(), pos=sv["pos"], pool_gen=sv["pool_gen"].clone(),
+                     gens=[g.clone() for g in sv["gens"]])
+        rem = [(lw["shared_rem"][0].clone(), lw["shared_rem"][1].clone()) for lw in self.layers]
+        return self.prefix_pool.snapshot(), rem, saved
+
+    def snapshot(self, what: str = "all"):
+        """The decoder's cache state as a snapshot.DecoderSnapshot (packed blobs: gear_cache_snapshot, one launch per pool).
+        what="prefix" (a shared-prefix decoder after prefill_shared()): the stored prompt -- the prefix pool, the per-layer
+        remainder rows and what reset_shared() restores (ids, logits row, pos, tail generator states): load_prefix() puts it into
+        any decoder of the same model and configuration.  what="all": additionally the tails (the whole cache of a plain decoder),
+        pos and shared_live: restore() resumes generation bit for bit where the snapshot was taken."""
+        from .snapshot import DecoderSnapshot
+        self._snapshot_refused("snapshot()")
+        if what not in ("all", "prefix"):
+            raise ValueError(f"snapshot(): what = {what!r}: 'all' or 'prefix'")
+        has_prefix = self.prefix_pool is not None and self._shared_saved is not None
+        if what == "prefix" and not has_prefix:
+            raise ValueError("snapshot('prefix'): needs a shared-prefix decoder (shared_prefix_tokens > 0) after prefill_shared()")
+        prefix, rem, saved = self._prefix_parts() if has_prefix else (None, None, None)
+        if what == "prefix":
+            return DecoderSnapshot("prefix", prefix, rem, saved)
+        return DecoderSnapshot("all", prefix, rem, saved, self.pool.snapshot(), self.pos, self.shared_live)
+
+    def _put_prefix(self, snap):
+        """Prefix pool, remainder rows and _shared_saved from a snapshot that holds a stored prompt (checked before any write)."""
+        from .snapshot import DecoderSnapshot
+        if not isinstance(snap, DecoderSnapshot) or snap.prefix is None:
+            raise ValueError("the snapshot holds no stored prompt (take it with snapshot('prefix') or snapshot('all') on a "
+                             "shared-prefix decoder after prefill_shared())")
+        if self.prefix_pool is None:
+            raise ValueError("a stored prompt needs a shared-prefix decoder (shared_prefix_tokens > 0)")
+        if len(snap.shared_rem) != len(self.layers) or len(snap.saved["gens"]) != len(self.layers):
+            raise ValueError(f"the snapshot holds {len(snap.shared_rem)} layers, this decoder has {len(self.layers)}")
+        self.prefix_pool.restore(snap.prefix)
+        for lw, (k, v) in zip(self.layers, snap.shared_rem):
+            lw["shared_rem"] = (k.to(self.dev), v.to(self.dev))
+        sv = snap.saved
+        self._shared_saved = dict(ids=sv["ids"].to(self.dev), logits=sv["logits"].to(self.dev), pos=int(sv["pos"]),
+                                  pool_gen=sv["pool_gen"], gens=list(sv["gens"]))
+        self._pending = None
+        self._state_dirty = True
+
+    def load_prefix(self, snap):
+        """Make `snap`'s stored prompt this decoder's: the prefix pool, the remainder rows and the reset point are restored (one
+        launch over the prompt's compressed bytes instead of a dense prefill), then reset_shared() empties the tails.  Works on a
+        decoder in any state -- fresh, or in the middle of generation over another prompt.  Afterwards the decoder is in the state
+        right after prefill_shared(ids): generate(ids, ..., shared_prefix=True, reuse_prefix=True), extend_shared() and
+        generate_beam() go on from there."""
+        self._snapshot_refused("load_prefix()")
+        self._put_prefix(snap)
+        self.shared_live = self.layers[0]["prefix"].n_comp > 0
+        self.reset_shared()
+
+    def restore(self, snap):
+        """Return to a snapshot.  what="all": the tails (the whole cache of a plain decoder) with their counters and generator
+        states, pos, shared_live and -- when it holds one -- the stored prompt: the steps that follow repeat, bit for bit, the
+        steps that followed the snapshot.  what="prefix": load_prefix()."""
+        from .snapshot import DecoderSnapshot, check_compatible, geometry_key
+        self._snapshot_refused("restore()")
+        if not isinstance(snap, DecoderSnapshot):
+            raise ValueError(f"restore(): expected a DecoderSnapshot, got {type(snap).__name__}")
+        if snap.what == "prefix":
+            return self.load_prefix(snap)
+        if snap.prefix is not None and self.prefix_pool is None:
+            raise ValueError("restore(): the snapshot holds a stored prompt, this decoder has no prefix pool")
+        p = self.pool                                           # the tails are checked before the stored prompt is written
+        check_compatible(snap.tail, geometry_key(p.dims, p.H, p.D), p.L, p.dims["Tmax"], p.dims["R"], "restore()")
+        if snap.tail.n_seq != p.B:
+            raise ValueError(f"restore(): the snapshot holds {snap.tail.n_seq} sequences, this decoder has batch {p.B}")
+        if snap.prefix is not None:
+            self._put_prefix(snap)
+        self.pool.restore(snap.tail)
+        self.pos, self.shared_live = snap.pos, snap.shared_live
+        self._pending = None
+        self._state_dirty = True
+
     def generate_beam(self, input_ids: torch.Tensor, max_length: int, num_beams: int = None, eos_token_id: int = None,
                       length_penalty: float = 1.0, num_return_sequences: int = 1, pad_token_id: int = 0):
         """Beam search with `batch` beams over ONE prompt input_ids [1, T] (a decoder built with shared_prefix_tokens > 0;

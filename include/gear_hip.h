@@ -464,6 +464,26 @@ int gear_attn_extend_shared(const gear_cache_view* prefix, int Tp, const gear_ca
 size_t gear_cache_reorder_workspace(const gear_cache_view* c, int n_layers, int batch, int T, int W);
 int gear_cache_reorder(const gear_cache_view* c, int n_layers, int batch, int T, int W, const int32_t* src_idx, void* workspace,
                        size_t workspace_bytes, void* stream);
+/* ---- snapshots: the live per-sequence state of a cache as one packed blob, and back ----------------------------------------------
+ * The blob is the live state (the fields and live ranges gear_cache_reorder moves, same c / n_layers / batch / T / W) of sequences
+ * seq0 .. seq0 + n_seq - 1 of every layer.  It has no header -- the caller keeps T, W, seg0 and kk0.  Layout: the fields in the
+ * order kcode, kscale, kmn, vcode, vscale, vmn, kP, kQ, vP, vQ, koidx, koval, kochunk, voidx, voval, vochunk, ktile, kcnt, vtile,
+ * vcnt, kwin, vwin (those the view has); within a field (outer index = layer [, factor segment], sequence, row); each row its live
+ * bytes rounded up to 16 (the padding is zero); rows that are live to their end, or whose pitch lies within one 128-byte line, are
+ * one run per sequence.  The layout is a function of (the view's geometry, kk0, seg0, n_layers, T, W, n_seq) alone.
+ *   gear_cache_snapshot_bytes: the blob's size (a multiple of 16, linear in n_seq; host only; 0 for an invalid shape)
+ *   gear_cache_snapshot: fields -> blob, ONE launch
+ *   gear_cache_restore:  blob -> fields of sequences seq0 .. seq0 + n_seq - 1, ONE launch.  blob_seqs == n_seq: sequence j of the
+ *            blob goes to sequence seq0 + j; blob_seqs == 1: the blob's one sequence goes to all n_seq destinations (a fork);
+ *            anything else is an argument error.  Only the live ranges of the destination sequences are written.
+ *   blob     DEVICE memory, 16-byte aligned (anything else is an argument error), at least gear_cache_snapshot_bytes(c, n_layers,
+ *            batch, T, W, n_seq resp. blob_seqs) bytes
+ * Neither call reads an index from device memory or synchronises. */
+size_t gear_cache_snapshot_bytes(const gear_cache_view* c, int n_layers, int batch, int T, int W, int n_seq);
+int gear_cache_snapshot(const gear_cache_view* c, int n_layers, int batch, int T, int W, int seq0, int n_seq, void* blob,
+                        size_t blob_bytes, void* stream);
+int gear_cache_restore(const gear_cache_view* c, int n_layers, int batch, int T, int W, int seq0, int n_seq, const void* blob,
+                       size_t blob_bytes, int blob_seqs, void* stream);
 /* (Re)build the sparse tiles of K chunks [k_chunk0, k_chunk1) (128 tokens each) and V blocks [v_blk0, v_blk1) (64 tokens each) of a
  * cache that holds T compressed tokens: called after the prompt and after every appended block (the chunk the block lies in). */
 int gear_cache_tiles_build(const gear_cache_view* c, int T, int k_chunk0, int k_chunk1, int v_blk0, int v_blk1, void* stream);
