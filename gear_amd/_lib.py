@@ -39,6 +39,8 @@ SIGNATURES = {
     "gear_attn_extend_cache": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, C.c_float, _vp, _vp, _vp, _sz, _vp]),
     "gear_attn_verify_workspace": (_sz, [_i, _i, _i, _i, _i]),
     "gear_attn_verify_cache": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, C.c_float, _vp, _vp, _vp, _sz, _vp]),
+    "gear_attn_verify_tree_workspace": (_sz, [_i, _i, _i, _i, _i]),
+    "gear_attn_verify_tree": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, C.c_float, _vp, _vp, _vp, _sz, _vp]),
     "gear_attn_decode_shared_workspace": (_sz, [_i, _i, _i, _i, _i]),
     "gear_attn_decode_shared": (_i, [_vp, _i, _vp, _i, _i, _vp, _i, C.c_float, _vp, _vp, _vp, _sz, _vp]),
     "gear_attn_extend_shared_workspace": (_sz, [_i, _i, _i, _i, _i, _i]),

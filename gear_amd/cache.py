@@ -317,6 +317,19 @@ def _check_room(c, n):
                           "capacity exceeded")
 
 
+def _tree_mask(anc, B, n, dev):
+    """anc of an attend_verify_tree call -> contiguous 32-bit device tensor [B, n] ([n]: the same tree for every sequence)."""
+    if not isinstance(anc, torch.Tensor) or anc.dtype not in (torch.int32, torch.uint32) or anc.device != dev:
+        raise ValueError(f"attend_verify_tree: anc must be an int32 / uint32 tensor on {dev}")
+    if anc.dtype == torch.uint32:
+        anc = anc.view(torch.int32)           # (the same bits; torch has few uint32 operators)
+    if anc.dim() == 1 or (anc.dim() == 2 and anc.shape[0] == 1 and B > 1):
+        anc = anc.reshape(1, -1).expand(B, -1)
+    if tuple(anc.shape) != (B, n):
+        raise ValueError(f"attend_verify_tree: anc must be [{B}, {n}] or [{n}], got {list(anc.shape)}")
+    return anc.contiguous()
+
+
 def _reorder_index(src_idx, B, dev):
     """src_idx of a reorder call -> int32 device tensor [B].  A host list or CPU tensor is checked here (every entry in [0, B));
     a device tensor is not read on the host -- gear_cache_reorder treats an entry outside [0, B) as identity."""
@@ -668,6 +681,40 @@ class GearKVCache:
         L.check(rc, "gear_attn_verify_cache")
         return (out, lse) if return_lse else out
 
+    def attend_verify_tree(self, q: torch.Tensor, k_new: torch.Tensor, v_new: torch.Tensor, anc: torch.Tensor,
+                           return_lse: bool = False):
+        """attend_verify over a draft tree (gear_attn_verify_tree): row i attends over the cache and those chunk rows j whose bit j
+        is set in anc[b, i] -- anc int32 / uint32 device tensor [B, n] (speculative.tree_layout), an [n] tensor serves every
+        sequence.  The kernel forces bit i and drops the bits above it.  Workspace and view are attend_verify's.  Changes no state."""
+        B, Hq, n = q.shape[0], q.shape[1], q.shape[2]
+        if n > N_MAX_VERIFY:
+            raise ValueError(f"attend_verify_tree: n = {n} query tokens, at most N_MAX_VERIFY = {N_MAX_VERIFY}")
+        _check_rows(k_new, v_new, self.B, self.H, self.D, n)
+        if tuple(q.shape) != (self.B, Hq, n, self.D) or q.dtype != torch.float16:
+            raise ValueError(f"attend_verify_tree: q must be fp16 [{self.B}, Hq, {n}, {self.D}], got {list(q.shape)} {q.dtype}")
+        anc = _tree_mask(anc, self.B, n, q.device)
+        lib = L.load()
+        q, k_new, v_new = q.contiguous(), k_new.contiguous(), v_new.contiguous()
+        out = torch.empty_like(q)
+        lse = torch.empty((B, Hq, n), dtype=torch.float32, device=q.device) if return_lse else None
+        wsb = lib.gear_attn_verify_tree_workspace(B, Hq, n, self.n_comp, self.n_win)
+        if self._vws is None or self._vws.numel() < wsb:
+            self._vws = torch.empty((wsb,), dtype=torch.uint8, device=q.device)
+        key = (self.kk0, self.seg0, True, self.use_tiles, self.use_chunk_index)
+        view = self._views.get(key)
+        if view is None:
+            view = _view(self.bufs, self.dims, B, self.H, self.D, self.kk0, self.seg0, kwin=True)
+            if not self.use_tiles:
+                view.ktile = view.vtile = None
+            if not self.use_chunk_index:
+                view.kochunk = view.vochunk = None
+            self._views[key] = view
+        rc = lib.gear_attn_verify_tree(C_.byref(view), L.ptr(q), Hq, n, self.n_comp, self.n_win, L.ptr(k_new), L.ptr(v_new),
+                                       L.ptr(anc), 1.0 / math.sqrt(self.D), L.ptr(out), L.ptr(lse), L.ptr(self._vws),
+                                       self._vws.numel(), L.stream_ptr(q))
+        L.check(rc, "gear_attn_verify_tree")
+        return (out, lse) if return_lse else out
+
     def attend_shared(self, q: torch.Tensor, prefix: "GearKVCache", return_lse: bool = False):
         """Shared-prefix decode attention: this cache (batch S) holds what each of S sequences appended after ONE common prompt,
         `prefix` (a GearKVCache with batch 1, an empty window and the same compress config) holds that prompt's compressed tokens.
@@ -854,6 +901,28 @@ class Fp16KVCache:
             k = k.repeat_interleave(Hq // self.H, 1)
         s = torch.einsum("bhid,bhtd->bhit", q.float(), k) / math.sqrt(self.D)
         mask = torch.ones((n, self.n_win + n), dtype=torch.bool, device=q.device).tril(self.n_win)
+        return out, torch.logsumexp(s.masked_fill(~mask, float("-inf")), -1)
+
+    def attend_verify_tree(self, q: torch.Tensor, k_new: torch.Tensor, v_new: torch.Tensor, anc: torch.Tensor,
+                           return_lse: bool = False):
+        """GearKVCache.attend_verify_tree on the baseline: torch SDPA with a boolean mask built from anc (bit i forced, the bits
+        above i dropped, as the kernel does); not a product path.  Changes no state."""
+        n, Hq = q.shape[2], q.shape[1]
+        if n > N_MAX_VERIFY:
+            raise ValueError(f"attend_verify_tree: n = {n} query tokens, at most N_MAX_VERIFY = {N_MAX_VERIFY}")
+        _check_rows(k_new, v_new, self.B, self.H, self.D, n)
+        row = torch.arange(n, device=q.device)
+        m = (_tree_mask(anc, self.B, n, q.device).long() & 0xFFFFFFFF | (1 << row)) & ((2 << row) - 1)          # [B, n]
+        mask = torch.cat([torch.ones((self.B, n, self.n_win), dtype=torch.bool, device=q.device),
+                          (m[:, :, None] >> row) & 1 != 0], 2)[:, None]                                          # [B, 1, n, W + n]
+        k = torch.cat([self.kwin[:, :, :self.n_win], k_new], 2)
+        v = torch.cat([self.vwin[:, :, :self.n_win], v_new], 2)
+        if Hq != self.H:
+            k, v = k.repeat_interleave(Hq // self.H, 1), v.repeat_interleave(Hq // self.H, 1)
+        out = torch.nn.functional.scaled_dot_product_attention(q, k, v, attn_mask=mask)
+        if not return_lse:
+            return out
+        s = torch.einsum("bhid,bhtd->bhit", q.float(), k.float()) / math.sqrt(self.D)
         return out, torch.logsumexp(s.masked_fill(~mask, float("-inf")), -1)
 
     def extend(self, k_new: torch.Tensor, v_new: torch.Tensor):

@@ -2326,7 +2326,8 @@ extern "C" int gear_attn_decode_cache(const gear_cache_view* c, const void* q, i
 // its KV head only through hq / (Hq / Hkv), so q [B, Hq, n, 128] goes to the decode partial dispatch as [B, Hq n, 128]: G n query rows
 // per KV head, every row's compressed-part (and, where the plan puts it there, window) partials computed by the unchanged kernels --
 // the matrix-core kernel reads and reconstructs each compressed chunk once for all of them when G n is 2, 4 or 8.  The merge below
-// then adds what only differs between the rows: chunk rows 0 .. i of the draft (causal).
+// then adds what only differs between the rows: chunk rows 0 .. i of the draft (causal), or -- gear_attn_verify_tree -- those of
+// them that a per-row mask names (a draft tree: the row's ancestors and itself).
 namespace {
 
 constexpr int VN_MAX = 16;              // query tokens per verify call
@@ -2346,10 +2347,17 @@ struct VerifyMerge {
     float qscale;
     uint16_t* out;                      // [B Hq n, 128]
     float* lse;                         // [B Hq n] or null
+    const uint32_t* anc;                // TREE only: [B, n] chunk-row masks (last: the chain kernel's argument offsets stay)
 };
 
 // one output row x = (b, hq, i) per workgroup: scores of the Wm window rows and chunk rows 0 .. i (8 threads per key, 16 channels
-// each), one fp32 softmax with the slots' (m, l), then the weighted sum (two groups of 128 channel threads)
+// each), one fp32 softmax with the slots' (m, l), then the weighted sum (two groups of 128 channel threads).
+// TREE: chunk row j takes part only where bit j of the row's mask is set.  The mask is sanitised -- bit i forced, the bits above i
+// dropped -- so the softmax is never empty, no row reads a row after itself and the key loops still end at Wm + i + 1.  A masked
+// key is skipped (no score, no part in the max, the sum or the output; sc[k] stays unwritten and unread); the keys that remain
+// are visited in the chain kernel's order, so the chain mask repeats its arithmetic.  The skip sits inside the k < nk guards:
+// every lane still reaches the __shfl_xor reductions.
+template <bool TREE>
 __global__ __launch_bounds__(256) void attn_verify_merge_kernel(VerifyMerge v) {
     __shared__ float qs[AD];
     __shared__ float sc[VK_MAX];
@@ -2364,6 +2372,9 @@ __global__ __launch_bounds__(256) void attn_verify_merge_kernel(VerifyMerge v) {
     const int b = (int)(bhq / v.Hq), hq = (int)(bhq % v.Hq);
     const int64_t bhk = (int64_t)b * v.Hkv + hq / (v.Hq / v.Hkv);
     const int nk = v.Wm + i + 1;
+    uint32_t msk = 0;
+    if constexpr (TREE) msk = (v.anc[(int64_t)b * v.n + i] | 1u << i) & ((2u << i) - 1u);      // (i <= 15)
+    const auto in = [&](int k) { return !TREE || k < v.Wm || ((msk >> (k - v.Wm)) & 1u) != 0; };     // key k takes part
     if (tid < AD) qs[tid] = h2f_bits(v.q[x * AD + tid]) * v.qscale;
     if (tid < v.ns) {
         sml[0][tid] = v.part_ml[(x * v.pslots + tid) * 2];
@@ -2374,7 +2385,7 @@ __global__ __launch_bounds__(256) void attn_verify_merge_kernel(VerifyMerge v) {
     for (int k0 = 0; k0 < nk; k0 += 32) {                  // (block-uniform)
         const int k = k0 + kj;
         float acc = 0.0f;
-        if (k < nk) {
+        if (k < nk && in(k)) {
             const uint16_t* kr = k < v.Wm ? v.kwin + (bhk * v.wcap + k) * (int64_t)AD : v.knew + (bhk * v.n + k - v.Wm) * (int64_t)AD;
             const uint4* kr4 = (const uint4*)(kr + part * 16);
             float t[8];
@@ -2388,13 +2399,14 @@ __global__ __launch_bounds__(256) void attn_verify_merge_kernel(VerifyMerge v) {
         acc += __shfl_xor(acc, 4, 64);
         acc += __shfl_xor(acc, 2, 64);
         acc += __shfl_xor(acc, 1, 64);
-        if (k < nk && part == 0) sc[k] = acc;
+        if (k < nk && in(k) && part == 0) sc[k] = acc;
     }
     __syncthreads();
     if (tid < 64) {   // statistics over <= 66 slots and <= 144 keys, strided over the 64 lanes of wave 0
         float M = -INFINITY;
         for (int s = tid; s < v.ns; s += 64) M = fmaxf(M, sml[0][s]);
-        for (int k = tid; k < nk; k += 64) M = fmaxf(M, sc[k]);
+        for (int k = tid; k < nk; k += 64)
+            if (in(k)) M = fmaxf(M, sc[k]);
 #pragma unroll
         for (int o = 32; o >= 1; o >>= 1) M = fmaxf(M, __shfl_xor(M, o, 64));
         float Ls = 0.0f;
@@ -2404,6 +2416,7 @@ __global__ __launch_bounds__(256) void attn_verify_merge_kernel(VerifyMerge v) {
             Ls = fmaf(c, sml[1][s], Ls);
         }
         for (int k = tid; k < nk; k += 64) {
+            if (!in(k)) continue;
             const float c = __expf(sc[k] - M);
             coef[RS_MAX + k] = c;
             Ls += c;
@@ -2417,6 +2430,7 @@ __global__ __launch_bounds__(256) void attn_verify_merge_kernel(VerifyMerge v) {
     float o = 0.0f;
     for (int s = grp; s < v.ns; s += 2) o = fmaf(coef[s], v.part_o[(x * v.pslots + s) * AD + d], o);
     for (int k = grp; k < nk; k += 2) {
+        if (!in(k)) continue;
         const uint16_t* vr = k < v.Wm ? v.vwin + (bhk * v.wcap + k) * (int64_t)AD : v.vnew + (bhk * v.n + k - v.Wm) * (int64_t)AD;
         o = fmaf(coef[RS_MAX + k], h2f_bits(vr[d]), o);
     }
@@ -2435,25 +2449,30 @@ extern "C" size_t gear_attn_verify_workspace(int B, int Hq, int n, int T, int W)
     return gear_attn_decode_workspace(B, Hq * n, T, 2);       // the partial slots of B Hq n query rows
 }
 
-extern "C" int gear_attn_verify_cache(const gear_cache_view* c, const void* q, int Hq, int n, int T, int W, const void* k_new,
-                                      const void* v_new, float qscale, void* out, void* lse, void* workspace, size_t workspace_bytes,
-                                      void* stream) {
-    GEAR_CHECK_ARG(c, "gear_attn_verify_cache: null cache view");
-    GEAR_CHECK_ARG(n >= 1 && n <= VN_MAX, "gear_attn_verify_cache: n = %d query tokens, must be in [1, %d] (longer chunks: "
-                   "gear_attn_extend_cache)", n, VN_MAX);
-    GEAR_CHECK_ARG(c->D == AD, "gear_attn_verify_cache: head_dim %d, must be 128", c->D);
-    GEAR_CHECK_ARG(c->B > 0 && c->Hkv > 0, "gear_attn_verify_cache: B %d x Hkv %d", c->B, c->Hkv);
-    GEAR_CHECK_ARG(Hq > 0 && Hq % c->Hkv == 0, "gear_attn_verify_cache: Hq %d not a multiple of Hkv %d", Hq, c->Hkv);
-    GEAR_CHECK_ARG((int64_t)c->B * Hq * n <= 65535, "gear_attn_verify_cache: B %d x Hq %d x n %d query rows", c->B, Hq, n);
-    GEAR_CHECK_ARG(W >= 0 && W <= c->wcap && c->wcap <= 128, "gear_attn_verify_cache: W = %d window tokens, the window holds "
-                   "wcap = %d (at most 128)", W, c->wcap);
+namespace {
+
+// gear_attn_verify_cache (tree = false) and gear_attn_verify_tree: the argument checks, the compressed part through the decode
+// partial dispatch and the merge launch; only the merge kernel's instantiation differs
+int attn_verify_impl(const char* fn, bool tree, const gear_cache_view* c, const void* q, int Hq, int n, int T, int W,
+                     const void* k_new, const void* v_new, const void* anc, float qscale, void* out, void* lse, void* workspace,
+                     size_t workspace_bytes, void* stream) {
+    GEAR_CHECK_ARG(c, "%s: null cache view", fn);
+    GEAR_CHECK_ARG(n >= 1 && n <= VN_MAX, "%s: n = %d query tokens, must be in [1, %d] (longer chunks: "
+                   "gear_attn_extend_cache)", fn, n, VN_MAX);
+    GEAR_CHECK_ARG(c->D == AD, "%s: head_dim %d, must be 128", fn, c->D);
+    GEAR_CHECK_ARG(c->B > 0 && c->Hkv > 0, "%s: B %d x Hkv %d", fn, c->B, c->Hkv);
+    GEAR_CHECK_ARG(Hq > 0 && Hq % c->Hkv == 0, "%s: Hq %d not a multiple of Hkv %d", fn, Hq, c->Hkv);
+    GEAR_CHECK_ARG((int64_t)c->B * Hq * n <= 65535, "%s: B %d x Hq %d x n %d query rows", fn, c->B, Hq, n);
+    GEAR_CHECK_ARG(W >= 0 && W <= c->wcap && c->wcap <= 128, "%s: W = %d window tokens, the window holds "
+                   "wcap = %d (at most 128)", fn, W, c->wcap);
     GEAR_CHECK_ARG(T >= 0 && T <= c->tcap && T % 64 == 0,
-                   "gear_attn_verify_cache: T = %d compressed tokens, must be a multiple of 64 in [0, tcap = %d]", T, c->tcap);
-    GEAR_CHECK_ARG(q && k_new && v_new && out, "gear_attn_verify_cache: null q / k_new / v_new / out");
-    GEAR_CHECK_ARG(W == 0 || (c->kwin && c->vwin), "gear_attn_verify_cache: W > 0 needs the window tensors");
+                   "%s: T = %d compressed tokens, must be a multiple of 64 in [0, tcap = %d]", fn, T, c->tcap);
+    GEAR_CHECK_ARG(q && k_new && v_new && out, "%s: null q / k_new / v_new / out", fn);
+    GEAR_CHECK_ARG(W == 0 || (c->kwin && c->vwin), "%s: W > 0 needs the window tensors", fn);
+    GEAR_CHECK_ARG(!tree || anc, "%s: null anc (the per-row chunk masks, uint32 [B, n])", fn);
     const size_t need = gear_attn_verify_workspace(c->B, Hq, n, T, W);
-    GEAR_CHECK_ARG(workspace && workspace_bytes >= need, "gear_attn_verify_cache: workspace of %zu bytes, needs %zu "
-                   "(gear_attn_verify_workspace)", workspace_bytes, need);
+    GEAR_CHECK_ARG(workspace && workspace_bytes >= need, "%s: workspace of %zu bytes, needs %zu "
+                   "(gear_attn_verify_workspace)", fn, workspace_bytes, need);
     VerifyMerge m;
     m.ns = 0;
     m.pslots = 1;
@@ -2484,9 +2503,35 @@ extern "C" int gear_attn_verify_cache(const gear_cache_view* c, const void* q, i
     m.qscale = qscale;
     m.out = (uint16_t*)out;
     m.lse = (float*)lse;
-    hipLaunchKernelGGL(attn_verify_merge_kernel, dim3((unsigned)((int64_t)c->B * Hq * n)), dim3(256), 0, (hipStream_t)stream, m);
+    m.anc = (const uint32_t*)anc;
+    const dim3 grid((unsigned)((int64_t)c->B * Hq * n));
+    if (tree) {
+        hipLaunchKernelGGL(attn_verify_merge_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, m);
+    } else {
+        hipLaunchKernelGGL(attn_verify_merge_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, m);
+    }
     GEAR_CHECK_LAUNCH("attn_verify_merge");
     return 0;
+}
+
+}  // namespace
+
+extern "C" int gear_attn_verify_cache(const gear_cache_view* c, const void* q, int Hq, int n, int T, int W, const void* k_new,
+                                      const void* v_new, float qscale, void* out, void* lse, void* workspace, size_t workspace_bytes,
+                                      void* stream) {
+    return attn_verify_impl("gear_attn_verify_cache", false, c, q, Hq, n, T, W, k_new, v_new, nullptr, qscale, out, lse, workspace,
+                            workspace_bytes, stream);
+}
+
+extern "C" size_t gear_attn_verify_tree_workspace(int B, int Hq, int n, int T, int W) {
+    return gear_attn_verify_workspace(B, Hq, n, T, W);
+}
+
+extern "C" int gear_attn_verify_tree(const gear_cache_view* c, const void* q, int Hq, int n, int T, int W, const void* k_new,
+                                     const void* v_new, const void* anc, float qscale, void* out, void* lse, void* workspace,
+                                     size_t workspace_bytes, void* stream) {
+    return attn_verify_impl("gear_attn_verify_tree", true, c, q, Hq, n, T, W, k_new, v_new, anc, qscale, out, lse, workspace,
+                            workspace_bytes, stream);
 }
 
 // ------------------------------------------------------------------------------------------------------------------

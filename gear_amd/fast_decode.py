@@ -484,8 +484,131 @@ class FastGearDecoder:
         return m
 
     @torch.no_grad()
+    def verify_tree(self, input_ids: torch.Tensor, parents: torch.Tensor) -> torch.Tensor:
+        """verify() over a draft tree: input_ids [B, n] are the nodes' tokens (node 0 = the last committed token), parents long [n]
+        or [B, n] the tree (speculative.tree_layout's form, any device).  Node i runs at RoPE position pos + depth[b, i] and attends
+        over the cache and its own ancestors among the n rows (cache.attend_verify_tree).  Returns the logits of every node
+        [B, n, vocab]; every layer's n post-RoPE K / V rows and the parents are kept until accept_path(idx) commits one root path.
+        verify()'s refusals; room is needed for the deepest path only.  Changes no cache state."""
+        from .cache import N_MAX_VERIFY, _check_room
+        from .speculative import tree_layout
+        self._shared_refused("verify_tree()")
+        if self.tp_world > 1:
+            raise NotImplementedError("verify_tree(): head-sharded (tp_world > 1) verification is not implemented -- use step()")
+        if torch.cuda.is_current_stream_capturing():
+            raise NotImplementedError("verify_tree(): speculative verification cannot be captured in a graph (host-side counters)")
+        if self.pos == 0:
+            raise ValueError("verify_tree(): run prefill() first")
+        if input_ids.dim() != 2 or input_ids.shape[0] != self.batch or not 1 <= input_ids.shape[1] <= N_MAX_VERIFY:
+            raise ValueError(f"verify_tree(): input_ids must be [{self.batch}, n], 1 <= n <= {N_MAX_VERIFY}, "
+                             f"got {list(input_ids.shape)}")
+        B, n = input_ids.shape
+        par = parents.detach().cpu()
+        if par.shape[-1] != n or (par.dim() == 2 and par.shape[0] not in (1, B)):
+            raise ValueError(f"verify_tree(): parents must be [{n}] or [{B}, {n}], got {list(parents.shape)}")
+        anc, depth = tree_layout(par)                             # (on the host: n <= 16 nodes)
+        deepest = int(depth.max()) + 1
+        c0 = self.layers[0]["cache"]
+        if self.pool is not None:
+            _check_room(c0, deepest)
+        elif c0.n_win + deepest > c0.R:
+            raise L.GearError(f"verify_tree(): {deepest} tokens after {c0.n_win} exceed the fp16 cache's capacity {c0.R}")
+        self._pending = self._pending_tree = None
+        m = self.model.model
+        res = m.embed_tokens(input_ids).view(B * n, -1)          # the B n rows as step()'s batch rows
+        anc = anc.view(torch.int32).to(self.dev)
+        pos = self.pos + depth.to(self.dev)
+        Hq, Hkv, D = self.Hq, self.Hkv, self.D
+        ks, vs = [], []
+        for lw in self.layers:
+            qkv = self._norm_linear(res, lw["wqkv"]).view(B, n, -1)
+            q, k, v = qkv.split([Hq * D, Hkv * D, Hkv * D], dim=-1)
+            q = q.view(B, n, Hq, D).transpose(1, 2)
+            k = k.view(B, n, Hkv, D).transpose(1, 2)
+            v = v.reshape(B, n, Hkv, D).transpose(1, 2).contiguous()
+            cos, sin = lw["rotary"](v, pos)
+            q, k = apply_rotary_pos_emb(q, k, cos, sin)
+            q, k = q.contiguous(), k.contiguous()
+            a = lw["cache"].attend_verify_tree(q, k, v, anc)
+            ks.append(k)
+            vs.append(v)
+            res = self._linear_add(a.transpose(1, 2).reshape(B * n, Hq * D), lw["wo"], res)
+            act = self._norm_linear(res, lw["wgu"], swiglu=True)
+            res = self._linear_add(act, lw["wd"], res)
+        self._pending_tree = dict(ks=ks, vs=vs, n=n, pos=self.pos, parents=par.reshape(-1, n).expand(B, n))
+        return self._norm_linear(res, self.w_head).view(B, n, -1)
+
+    @torch.no_grad()
+    def accept_path(self, idx: torch.Tensor) -> int:
+        """Commit one root path of the last verify_tree(): idx long [m] or [B, m], 0 <= m <= n, node indices root first (idx[:, 0]
+        == 0, every next node a child of the one before -- checked on the host against the pending parents).  Those rows are
+        gathered along the token axis and committed exactly as accept(m) commits rows 0 .. m - 1; advances pos.  Returns m.
+        A verify_tree() is consumed by accept_path() only, a verify() by accept() only."""
+        self._shared_refused("accept_path()")
+        p = getattr(self, "_pending_tree", None)
+        if getattr(self, "_pending", None) is not None:
+            raise ValueError("accept_path(): the pending pass is a verify(): commit it with accept()")
+        if p is None or p["pos"] != self.pos:
+            raise ValueError("accept_path(): no pending verify_tree() (each can be accepted once, before any other step)")
+        B, n = p["parents"].shape
+        ix = torch.as_tensor(idx).detach().cpu()
+        if ix.dim() == 1:
+            ix = ix.unsqueeze(0).expand(B, -1)
+        if ix.dim() != 2 or ix.shape[0] != B or ix.dtype != torch.long or ix.shape[1] > n:
+            raise ValueError(f"accept_path(): idx must be long [m] or [{B}, m], m <= {n}, got {list(ix.shape)} {ix.dtype}")
+        m = ix.shape[1]
+        if m:
+            if bool((ix[:, 0] != 0).any()) or bool(((ix < 0) | (ix >= n)).any()) or \
+                    not torch.equal(p["parents"].gather(1, ix[:, 1:]), ix[:, :-1]):
+                raise ValueError("accept_path(): idx is no root path of the pending tree (idx[:, 0] == 0, parents[idx[:, j + 1]] "
+                                 "== idx[:, j])")
+        self._pending_tree = None
+        if m == 0:
+            return 0
+        gx = ix.to(self.dev)[:, None, :, None].expand(B, self.Hkv, m, self.D)
+        ks = [k.gather(2, gx) for k in p["ks"]]
+        vs = [v.gather(2, gx) for v in p["vs"]]
+        if self.pool is not None:
+            for _ in range(self.pool.extend_all(ks, vs)):
+                self._after_boundary()
+        else:
+            for lw, k, v in zip(self.layers, ks, vs):
+                lw["cache"].extend(k, v)
+        self.pos += m
+        self._state_dirty = True          # a later step_graph() brings the device-side state up to date
+        return m
+
+    def _generate_tree(self, input_ids, max_length, n_draft, width, return_stats):
+        """generate_speculative's loop over draft trees (tree_width > 1, the n-gram drafter, greedy acceptance)."""
+        from .cache import N_MAX_VERIFY
+        from .speculative import ngram_tree_draft, tree_accept
+        n_draft = min(n_draft, N_MAX_VERIFY - 1)
+        out = torch.cat([input_ids, self.prefill(input_ids).argmax(-1, keepdim=True)], 1)
+        passes = drafted = accepted = 0
+        while out.shape[1] < max_length:
+            k = max(0, min(n_draft, max_length - out.shape[1] - 1, self._room() - 1))
+            d, par = ngram_tree_draft(out, k + 1, width)
+            nodes = torch.cat([out[:, -1:], d.to(out.dtype)], 1)
+            lg = self.verify_tree(nodes, par)
+            path, length, _ = tree_accept(nodes, par, lg)
+            a = int(length.min()) - 1                               # the batch's minimum number of accepted drafts
+            path = path[:, :a + 1]                                  # every row: its own path, cut to that length
+            self.accept_path(path)
+            # the argmax at the path's nodes = the row's accepted drafts, then the model's own token after them
+            out = torch.cat([out, lg.argmax(-1).gather(1, path).to(out.dtype)], 1)
+            passes += 1
+            drafted += k
+            accepted += a
+        self.check_block_kernel()
+        if not return_stats:
+            return out
+        gen = out.shape[1] - input_ids.shape[1]
+        return out, dict(passes=passes, tokens=gen, tokens_per_pass=(gen - 1) / max(passes, 1), drafted=drafted, accepted=accepted,
+                         acceptance_rate=accepted / max(drafted, 1))
+
+    @torch.no_grad()
     def generate_speculative(self, input_ids: torch.Tensor, max_length: int, draft="ngram", n_draft: int = 3,
-                             return_stats: bool = False, sampling=None):
+                             return_stats: bool = False, sampling=None, tree_width: int = 1):
         """Greedy decoding with speculative verification: each pass drafts k <= n_draft tokens (draft = "ngram":
         speculative.ngram_draft over the tokens so far, or a callable (tokens [B, L], k) -> [B, k]), verifies [last token, d1 .. dk]
         in one verify() and commits the accepted drafts + the model's next token (accept(a + 1)).  With batch > 1 every row commits
@@ -495,10 +618,21 @@ class FastGearDecoder:
         sampling (a sampling.SamplingParams): speculative sampling instead of greedy acceptance -- ONE gear_sample_tokens call over
         the verify logits [B, k + 1, V] accepts draft d_i with probability p(d_i) at its position and otherwise draws from p without
         d_i (the bonus row draws from p): every emitted token is an exact sample from the filtered distribution.  a = the batch
-        minimum of leading accepts; a row that accepted further emits its draft at a, a row rejected at a its residual draw."""
+        minimum of leading accepts; a row that accepted further emits its draft at a, a row rejected at a its residual draw.
+        tree_width > 1 (draft = "ngram", greedy only): every pass drafts a TREE of n_draft + 1 nodes (speculative.ngram_tree_draft:
+        up to tree_width continuations of the trailing n-gram under one root), checks it in one verify_tree() pass, walks it with
+        speculative.tree_accept and commits the batch's minimum path length through accept_path(), each row its own path."""
         from .speculative import accepted_lengths, ngram_draft
         if self.shared_prefix_tokens:
             raise NotImplementedError("generate_speculative(): not implemented for a shared-prefix decoder (shared_prefix_tokens > 0)")
+        if tree_width > 1:
+            if sampling is not None:
+                raise NotImplementedError("generate_speculative(): sampling over a draft tree (tree_width > 1) is not implemented")
+            if draft != "ngram" or n_draft < 0:
+                raise ValueError(f"generate_speculative: tree_width = {tree_width} needs draft='ngram' and n_draft >= 0")
+            return self._generate_tree(input_ids, max_length, n_draft, tree_width, return_stats)
+        if tree_width < 1:
+            raise ValueError(f"generate_speculative: tree_width = {tree_width}")
         if draft == "ngram":
             drafter = ngram_draft
         elif callable(draft):

@@ -106,7 +106,11 @@ def run(variant, args, dev):
     elif variant == "gearl" and args.fast:
         from gear_amd.fast_decode import FastGearDecoder
         dec = FastGearDecoder(model, args.max_length + 8, batch=args.batch_size)
-        out = dec.generate(ids, args.max_length, **fast_kw)
+        if args.tree_width:
+            # speculative decoding with prompt-lookup drafts: chains (1) or draft trees of this width (verify_tree / accept_path)
+            out = dec.generate_speculative(ids, args.max_length, draft="ngram", n_draft=7, tree_width=args.tree_width, **fast_kw)
+        else:
+            out = dec.generate(ids, args.max_length, **fast_kw)
         cache_bytes = sum(t.numel() * t.element_size() for t in dec.pool.buf.values())
         del dec
     elif variant == "None" and args.fast:
@@ -158,6 +162,9 @@ def main():
     ap.add_argument("--num_beams", type=int, default=0,
                     help="with --fast --shared_prefix: beam search with this many beams over the one prompt (generate_beam)")
     ap.add_argument("--length_penalty", type=float, default=1.0, help="beam scores are divided by length ** length_penalty")
+    ap.add_argument("--tree_width", type=int, default=0,
+                    help="with --fast: generate_speculative with n-gram drafts (n_draft 7); 1: draft chains, N > 1: draft trees of "
+                         "up to N continuations per pass (greedy only)")
     ap.add_argument("--json", action="store_true")
     # sampling, with the defaults of GenerationBench/GenerationTest/evaluation_bbh_cot.py:381-390
     ap.add_argument("--do_sample", action="store_true", help="sample (temperature / top-k / top-p) instead of greedy decoding")
@@ -174,6 +181,10 @@ def main():
         raise SystemExit("--num_beams and --do_sample exclude each other (beam search is deterministic)")
     if args.num_beams < 0:
         raise SystemExit("--num_beams must be positive")
+    if args.tree_width < 0 or (args.tree_width and (not args.fast or args.shared_prefix)):
+        raise SystemExit("--tree_width needs --fast without --shared_prefix (speculative decoding lives in FastGearDecoder)")
+    if args.tree_width > 1 and args.do_sample:
+        raise SystemExit("--tree_width > 1 and --do_sample exclude each other (sampling over a draft tree is not implemented)")
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
     variants = ["gearl", "KIVI", "None"] if args.all else [v for v in ("gearl", "KIVI", "None") if v in args.model]

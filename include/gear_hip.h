@@ -413,6 +413,20 @@ size_t gear_attn_verify_workspace(int B, int Hq, int n, int T, int W);
 int gear_attn_verify_cache(const gear_cache_view* c, const void* q, int Hq, int n, int T, int W, const void* k_new,
                            const void* v_new, float qscale, void* out, void* lse, void* workspace, size_t workspace_bytes,
                            void* stream);
+/* ---- tree verify: the n <= 16 rows are the nodes of a draft tree -------------------------------------------------------------
+ * gear_attn_verify_cache with one change: output row (b, hq, i) is one fp32 softmax over the T compressed tokens, the W window
+ * tokens and those chunk rows j whose bit j is set in anc[b, i] (row i's ancestors in the tree and row i itself), not chunk rows
+ * 0 .. i.  The caller lists the nodes in a topological order (bit j set only for j <= i, bit i set); the kernel does not rely on
+ * it and uses m = (anc[b, i] | 1u << i) & ((2u << i) - 1): no mask gives an empty softmax or lets a row read a row after itself.
+ * A masked row is skipped, not weighted by zero; the rows that remain are added in gear_attn_verify_cache's order, so the chain
+ * mask (2u << i) - 1 repeats its arithmetic.  The compressed part runs through the same partial dispatch (the mask does not touch
+ * it); arguments, checks, options and launches are gear_attn_verify_cache's, plus
+ *   anc    uint32 [B, n], device (not NULL)
+ *   workspace: gear_attn_verify_tree_workspace(B, Hq, n, T, W) bytes (= gear_attn_verify_workspace). */
+size_t gear_attn_verify_tree_workspace(int B, int Hq, int n, int T, int W);
+int gear_attn_verify_tree(const gear_cache_view* c, const void* q, int Hq, int n, int T, int W, const void* k_new,
+                          const void* v_new, const void* anc, float qscale, void* out, void* lse, void* workspace,
+                          size_t workspace_bytes, void* stream);
 /* ---- shared-prefix decode: S sequences over ONE stored prompt ----------------------------------------------------------------
  * `prefix` is a view with B == 1 that holds the prompt's Tp compressed tokens (no window is read from it); `tail` is a view with
  * B == S of the same configuration (Hkv, D, bits, group, mode, ranks) that holds what every sequence appended since: T compressed
