@@ -99,6 +99,10 @@ SIGNATURES = {
     "gear_xchg_close": (_i, [_vp]),
     "gear_xchg_allgather": (_i, [_vp, _i, _sz, _i, _i, _vp, _vp, _vp, _vp]),
     "gear_sample_tokens": (_i, [_vp, _i, _i, _i, _i64, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gear_kivi_rope_append": (_i, [_vp, _i, _i, _i, _i, _i, C.c_float, _vp, _vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "gear_kivi_append": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "gear_attn_decode_kivi_workspace": (_sz, [_i, _i, _i, _i]),
+    "gear_attn_decode_kivi": (_i, [_vp, _vp, _i, _i, _i, _i, C.c_float, _vp, _vp, _vp, _sz, _vp]),
 }
 
 ABI_VERSION = 5      # what this table was written against (gear_abi_version() of the library must match)

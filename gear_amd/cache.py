@@ -934,3 +934,191 @@ class Fp16KVCache:
         self.vwin[:, :, self.n_win:self.n_win + n] = v_new
         self.n_win += n
 
+
+
+class KiviKVCache:
+    """The KIVI baseline's cache for one attention layer on the fused decode path (csrc/kivi.hip): the state machine of the KIVI
+    attention hook (modeling_llama_kivi.py; cuda_supported_gear/modeling_llama_kivi.py:149-162, :200-248), pre-allocated.
+
+    K: an fp16 window `kwin` [B, Hkv, R, 128] that is quantized per channel as ONE block when it holds R = `residual` tokens
+       (maybe_compress(), eagerly between steps); the prompt is split at T - T % R.
+    V: a sliding fp16 window kept as a RING `vring` [B, Hkv, R + 1, 128] -- token t lives in row t % (R + 1).  The hook quantizes
+       the oldest of R + 1 rows right after the step's attention; here that row stays where it is until the NEXT token's append
+       overwrites it, and the append launch quantizes it first (gear_kivi_rope_append: no launch of its own).  Every attend()
+       therefore sees what the hook's attention sees: R + 1 fp16 rows and `n_vpacked` = L - (R + 1) packed rows.  The prompt keeps
+       its last R rows in fp16.
+    The packed fields have GearKVCache's layouts (kcode [B,Hkv,128,Tmax/fpi], kscale / kmn [B,Hkv,128,Tmax/group]; vcode
+    [B,Hkv,Tmax,128/fpi], vscale / vmn [B,Hkv,Tmax,128/group]): the decode partial kernels read them unchanged.
+
+    State (host counters): seq_len = L; n_kpacked (a multiple of R) and n_kwin = L - n_kpacked; n_vpacked rows written to vcode,
+    n_vwin = L - n_vpacked fp16 rows in the ring (at most R + 1), the oldest of them in row ring_start.  v_pending is 1 while the
+    ring holds R + 1 rows: the hook's tuple then already counts the oldest as packed (hook_counters())."""
+
+    def __init__(self, batch: int, n_kv_heads: int, max_tokens: int, bits: int, group: int, residual: int, device,
+                 head_dim: int = 128):
+        if head_dim != 128 or bits not in (2, 4) or group != 64 or residual not in (64, 128):
+            raise L.GearError(f"KiviKVCache: head_dim 128, bits 2 / 4, group 64 and residual 64 / 128 are built (got head_dim "
+                              f"{head_dim}, bits {bits}, group {group}, residual {residual})")
+        R = residual
+        self.B, self.H, self.D = batch, n_kv_heads, head_dim
+        self.bits, self.group, self.R = bits, group, R
+        self.fpi = 32 // bits
+        self.Tmax = (max_tokens + R - 1) // R * R
+        if self.Tmax > 16384 or max_tokens < 1:
+            raise L.GearError(f"KiviKVCache: capacity {max_tokens} tokens, must lie in [1, 16384]")
+        B, H, D, T, fpi = batch, n_kv_heads, head_dim, self.Tmax, self.fpi
+        z = lambda shp, dt: torch.zeros(shp, dtype=dt, device=device)
+        self.kcode, self.kscale, self.kmn = z((B, H, D, T // fpi), torch.int32), z((B, H, D, T // group), torch.float16), \
+            z((B, H, D, T // group), torch.float16)
+        self.vcode, self.vscale, self.vmn = z((B, H, T, D // fpi), torch.int32), z((B, H, T, D // group), torch.float16), \
+            z((B, H, T, D // group), torch.float16)
+        self.kwin = z((B, H, R, D), torch.float16)
+        self.vring = z((B, H, R + 1, D), torch.float16)
+        self.n_tok = 0           # L
+        self.n_kpacked = 0       # Tk
+        self.n_vpacked = 0       # Nv
+        self._ws = None
+        v = L.CacheView()
+        for f in ("kcode", "kscale", "kmn", "vcode", "vscale", "vmn", "kwin"):
+            setattr(v, f, L.ptr(getattr(self, f)))
+        v.vwin = L.ptr(self.vring)
+        v.B, v.Hkv, v.D, v.tcap = B, H, D, T
+        v.ldk, v.lsk, v.group, v.bits, v.mode, v.wcap = T // fpi, T // group, group, bits, 0, R
+        self._view = v
+
+    # ------------------------------------------------------------------------------------------------ state
+    @property
+    def seq_len(self) -> int:
+        return self.n_tok
+
+    @property
+    def n_kwin(self) -> int:
+        return self.n_tok - self.n_kpacked
+
+    @property
+    def n_vwin(self) -> int:
+        return self.n_tok - self.n_vpacked
+
+    @property
+    def ring_start(self) -> int:
+        """Ring row of the oldest fp16 V token (token n_vpacked)."""
+        return self.n_vpacked % (self.R + 1)
+
+    @property
+    def v_pending(self) -> int:
+        return 1 if self.n_vwin == self.R + 1 else 0
+
+    def hook_counters(self):
+        """(packed K tokens, fp16 K rows, packed V rows, fp16 V rows) as the hook's 9-slot tuple shows them after the same
+        tokens: the oldest of R + 1 ring rows counts as packed (the next append writes its codes)."""
+        return self.n_kpacked, self.n_kwin, self.n_vpacked + self.v_pending, self.n_vwin - self.v_pending
+
+    def ring_tokens(self) -> torch.Tensor:
+        """The fp16 V rows in token order: [B, Hkv, n_vwin, 128] (tokens n_vpacked .. L - 1)."""
+        idx = torch.arange(self.n_vpacked, self.n_tok, device=self.vring.device) % (self.R + 1)
+        return self.vring.index_select(2, idx)
+
+    def _quantize_k(self, k_rows: torch.Tensor, t0: int):
+        """k_rows fp16 [B, Hkv, n, 128] (n a multiple of R) -> codes, scales and minima of tokens [t0, t0 + n), per channel along
+        the tokens: the quantizer call of the hook (modeling_llama_kivi.py: K^T packed along its last dimension)."""
+        from .quant.new_pack import triton_quantize_and_pack_along_last_dim
+        n = k_rows.shape[2]
+        code, scale, mn = triton_quantize_and_pack_along_last_dim(k_rows.transpose(2, 3).contiguous(), self.group, self.bits)
+        self.kcode[:, :, :, t0 // self.fpi:(t0 + n) // self.fpi] = code
+        self.kscale[:, :, :, t0 // self.group:(t0 + n) // self.group] = scale
+        self.kmn[:, :, :, t0 // self.group:(t0 + n) // self.group] = mn
+
+    def prefill(self, k: torch.Tensor, v: torch.Tensor):
+        """k, v fp16 [B, Hkv, T, 128] (post-RoPE).  K: the first T - T % R tokens are packed, the rest go to the window.  V:
+        T <= R: every row stays fp16; otherwise the first T - R rows are packed per token and the last R go to the ring."""
+        from .quant.new_pack import triton_quantize_and_pack_along_last_dim
+        assert self.n_tok == 0
+        T, R = k.shape[2], self.R
+        if tuple(k.shape) != (self.B, self.H, T, self.D) or tuple(v.shape) != tuple(k.shape) or k.dtype != torch.float16 \
+                or v.dtype != torch.float16:
+            raise ValueError(f"KiviKVCache.prefill: K / V must be fp16 [{self.B}, {self.H}, T, {self.D}], got {list(k.shape)} "
+                             f"{k.dtype} / {list(v.shape)} {v.dtype}")
+        if T < 1 or T > self.Tmax:
+            raise L.GearError(f"KiviKVCache.prefill: {T} tokens, the cache holds {self.Tmax}")
+        nq = T - T % R
+        if nq:
+            self._quantize_k(k[:, :, :nq], 0)
+        if nq < T:
+            self.kwin[:, :, :T - nq] = k[:, :, nq:]
+        nv = max(0, T - R)
+        if nv:
+            code, scale, mn = triton_quantize_and_pack_along_last_dim(v[:, :, :nv].contiguous(), self.group, self.bits)
+            self.vcode[:, :, :nv], self.vscale[:, :, :nv], self.vmn[:, :, :nv] = code, scale, mn
+        idx = torch.arange(nv, T, device=v.device) % (R + 1)
+        self.vring.index_copy_(2, idx, v[:, :, nv:])
+        self.n_tok, self.n_kpacked, self.n_vpacked = T, nq, nv
+
+    def _evict_row(self) -> int:
+        """The vcode row the next append must write before it overwrites its ring row (-1: that row is free or already packed)."""
+        if self.n_kwin >= self.R:
+            raise L.GearError(f"KiviKVCache: the K window is full ({self.n_kwin} of {self.R} rows): call maybe_compress() after "
+                              "every step")
+        if self.n_kwin == self.R - 1 and self.n_kpacked + self.R > self.Tmax:
+            raise L.GearError(f"KiviKVCache: capacity reached ({self.n_tok} tokens; {self.Tmax} packed K tokens at most)")
+        row = self.n_tok - (self.R + 1)
+        return row if row >= self.n_vpacked else -1
+
+    def _appended(self, row):
+        if row >= 0:
+            self.n_vpacked = row + 1
+        self.n_tok += 1
+
+    def append_rope(self, qkv: torch.Tensor, n_q_heads: int, pos: int, theta: float) -> torch.Tensor:
+        """qkv fp16 [B, (Hq + 2 Hkv) * 128] of the new token -> RoPE, k into the K window, v into the ring (its evicted row
+        quantized in the same launch); returns q [B, Hq, 1, 128]."""
+        L.require_gpu(qkv)
+        row = self._evict_row()
+        q = torch.empty((self.B, n_q_heads, 1, self.D), dtype=torch.float16, device=qkv.device)
+        rc = L.load().gear_kivi_rope_append(L.ptr(qkv), self.B, n_q_heads, self.H, self.D, pos, theta, L.ptr(q), L.ptr(self.kwin),
+                                            self.n_kwin, L.ptr(self.vring), self.n_tok, self.R, row, L.ptr(self.vcode),
+                                            L.ptr(self.vscale), L.ptr(self.vmn), self.Tmax, self.group, self.bits,
+                                            L.stream_ptr(qkv))
+        L.check(rc, "gear_kivi_rope_append")
+        self._appended(row)
+        return q
+
+    def append(self, k_new: torch.Tensor, v_new: torch.Tensor):
+        """k_new, v_new fp16 [B, Hkv, 1, 128] (already rotated): gear_kivi_append, the same launch without the rotation."""
+        want = (self.B, self.H, 1, self.D)
+        if tuple(k_new.shape) != want or tuple(v_new.shape) != want or k_new.dtype != torch.float16 or v_new.dtype != torch.float16:
+            raise ValueError(f"KiviKVCache.append: K / V must be fp16 {list(want)}, got {list(k_new.shape)} / {list(v_new.shape)}")
+        k_new, v_new = k_new.contiguous(), v_new.contiguous()
+        L.require_gpu(k_new, v_new)
+        row = self._evict_row()
+        rc = L.load().gear_kivi_append(L.ptr(k_new), L.ptr(v_new), self.B, self.H, self.D, L.ptr(self.kwin), self.n_kwin,
+                                       L.ptr(self.vring), self.n_tok, self.R, row, L.ptr(self.vcode), L.ptr(self.vscale),
+                                       L.ptr(self.vmn), self.Tmax, self.group, self.bits, L.stream_ptr(k_new))
+        L.check(rc, "gear_kivi_append")
+        self._appended(row)
+
+    def attend(self, q: torch.Tensor, return_lse: bool = False):
+        """q fp16 [B, Hq, 1, 128] -> one fp32 softmax over all seq_len tokens (gear_attn_decode_kivi: packed K + K window, packed V
+        + ring), fp16 [B, Hq, 1, 128]; with return_lse also the fp32 [B, Hq] log-sum-exp of the scaled scores.  Two launches;
+        changes no state."""
+        B, Hq = q.shape[0], q.shape[1]
+        if tuple(q.shape) != (self.B, Hq, 1, self.D) or q.dtype != torch.float16:
+            raise ValueError(f"KiviKVCache.attend: q must be fp16 [{self.B}, Hq, 1, {self.D}], got {list(q.shape)} {q.dtype}")
+        q = q.contiguous()
+        L.require_gpu(q)
+        lib = L.load()
+        out = torch.empty((B, Hq, 1, self.D), dtype=torch.float16, device=q.device)
+        lse = torch.empty((B, Hq), dtype=torch.float32, device=q.device) if return_lse else None
+        wsb = lib.gear_attn_decode_kivi_workspace(B, Hq, self.Tmax, self.bits)
+        if self._ws is None or self._ws.numel() < wsb:
+            self._ws = torch.empty((wsb,), dtype=torch.uint8, device=q.device)
+        rc = lib.gear_attn_decode_kivi(C_.byref(self._view), L.ptr(q), Hq, self.n_tok, self.n_kpacked, self.n_vpacked,
+                                       1.0 / math.sqrt(self.D), L.ptr(out), L.ptr(lse), L.ptr(self._ws), self._ws.numel(),
+                                       L.stream_ptr(q))
+        L.check(rc, "gear_attn_decode_kivi")
+        return (out, lse) if return_lse else out
+
+    def maybe_compress(self):
+        """Quantize the K window as one block when it holds `residual` tokens (modeling_llama_kivi.py:95-103)."""
+        if self.n_kwin == self.R:
+            self._quantize_k(self.kwin, self.n_kpacked)
+            self.n_kpacked += self.R

@@ -18,6 +18,7 @@
 #include <math.h>
 #include <stdlib.h>
 
+#include "attn_partials.h"
 #include "common.h"
 #include "ktile.h"
 
@@ -2712,5 +2713,25 @@ extern "C" int gear_attn_decode_shared(const gear_cache_view* prefix, int Tp, co
     m.lse = (float*)lse;
     hipLaunchKernelGGL(attn_shared_merge_kernel, dim3((unsigned)((int64_t)S * Hq)), dim3(256), 0, (hipStream_t)stream, m);
     GEAR_CHECK_LAUNCH("attn_shared_merge");
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// The partial dispatch for kivi.hip (attn_partials.h): the whole 64-token chunks of a KIVI cache below its V seam are plain
+// quantized tokens -- rank 0, no outliers, no window -- and go through the same kernels as every other compressed token.
+int gear_attn_partials_dense(const gear_cache_view* c, const void* q, int Hq, int T, float qscale, void* workspace,
+                             size_t workspace_bytes, void* stream, gear_attn_partials* out) {
+    GEAR_CHECK_ARG(c && out, "gear_attn_partials_dense: null cache view");
+    GEAR_CHECK_ARG(T > 0 && T % 64 == 0 && T <= c->tcap, "gear_attn_partials_dense: T = %d, must be a positive multiple of 64 within "
+                   "tcap = %d", T, c->tcap);
+    AttnArgs a;
+    const int rc = attn_decode_impl(q, c->kcode, c->kscale, c->kmn, nullptr, nullptr, nullptr, nullptr, c->vcode, c->vscale, c->vmn,
+                                    nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, c->B, Hq, c->Hkv, c->D, T, 0, c->ldk, c->lsk,
+                                    c->tcap, c->tcap, c->tcap, c->group, c->bits, c->mode, 0, 0, 0, 0, 0, 0, 0, nullptr, qscale,
+                                    const_cast<void*>(q), nullptr, workspace, workspace_bytes, stream, nullptr, nullptr, nullptr, &a);
+    if (rc != 0) return rc;
+    out->part_o = a.part_o;
+    out->part_ml = a.part_ml;
+    out->pslots = a.pslots;
     return 0;
 }

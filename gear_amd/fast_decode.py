@@ -14,7 +14,7 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib as L
-from .cache import Fp16KVCache, GearKVCache, GearKVCachePool
+from .cache import Fp16KVCache, GearKVCache, GearKVCachePool, KiviKVCache
 from .modeling_llamagear import apply_rotary_pos_emb
 from .sampling import sample_tokens
 
@@ -37,7 +37,10 @@ class FastGearDecoder:
         compress call), "per_shard" = k / world inside the shard's own heads (rounds 1-3).
         cache_kind: "gear" (the compressed streaming cache) or "fp16" = cache.Fp16KVCache, the uncompressed baseline the reference's
         harness times beside the compressed models (cuda_supported_gear/test.py:41-62: model "None"): same weights, same fused GEMVs,
-        same attention split / merge kernels over fp16 rows; eager steps on one GPU only.
+        same attention split / merge kernels over fp16 rows; eager steps on one GPU only.  "kivi" = cache.KiviKVCache, the KIVI
+        baseline of that harness (modeling_llama_kivi.py's state machine: K block window, sliding fp16 V window) on csrc/kivi.hip --
+        bits, group and residual length are the attention modules' (k_bits, group_size, residual_length), as the KIVI hook takes
+        them; prefill / step / generate with eager steps on one GPU, everything else raises NotImplementedError.
         shared_prefix_tokens > 0: shared-prefix decoding -- `batch` sequences continue ONE prompt.  A second cache pool with batch 1
         and that capacity holds the prompt's compressed tokens once (same per-layer seeds: its payload is bit-identical to segment 0
         of a plain batch-1 decoder); `max_tokens` then sizes only the per-sequence tails.  prefill_shared() fills both, step() then
@@ -62,15 +65,19 @@ class FastGearDecoder:
         # pooled cache storage: block boundaries compress every layer's window in one launch sequence
         if v_selection not in ("exact", "per_shard"):
             raise ValueError(f"v_selection {v_selection!r}: 'exact' or 'per_shard'")
-        if cache_kind not in ("gear", "fp16"):
-            raise ValueError(f"cache_kind {cache_kind!r}: 'gear' or 'fp16'")
+        if cache_kind not in ("gear", "fp16", "kivi"):
+            raise ValueError(f"cache_kind {cache_kind!r}: 'gear', 'fp16' or 'kivi'")
         if cache_kind == "fp16" and tp_world > 1:
             raise NotImplementedError("the fp16-cache baseline runs on one GPU")
+        if cache_kind == "kivi" and tp_world > 1:
+            raise NotImplementedError("the KIVI cache (cache_kind='kivi') runs on one GPU (tp_world > 1 is not implemented)")
         self.cache_kind = cache_kind
         if shared_prefix_tokens < 0:
             raise ValueError(f"shared_prefix_tokens = {shared_prefix_tokens}")
         if shared_prefix_tokens and cache_kind == "fp16":
             raise NotImplementedError("shared-prefix decoding is not implemented for the fp16-cache baseline (cache_kind='fp16')")
+        if shared_prefix_tokens and cache_kind == "kivi":
+            raise NotImplementedError("shared-prefix decoding is not implemented for the KIVI cache (cache_kind='kivi')")
         if shared_prefix_tokens and tp_world > 1:
             raise NotImplementedError("shared-prefix decoding is not implemented for head-sharded decoders (tp_world > 1)")
         self.shared_prefix_tokens = int(shared_prefix_tokens)
@@ -78,7 +85,7 @@ class FastGearDecoder:
         self.prefix_pool = None
         self._shared_saved = None     # what reset_shared() restores: set by prefill_shared()
         tp = dict(rank=tp_rank, world=tp_world, group=tp_group, exact=v_selection == "exact") if tp_world > 1 else None
-        self.pool = None if cache_kind == "fp16" else GearKVCachePool(len(model.model.layers), batch, self.Hkv, max_tokens, cc0, dev,
+        self.pool = None if cache_kind != "gear" else GearKVCachePool(len(model.model.layers), batch, self.Hkv, max_tokens, cc0, dev,
                                                                       self.D, seed=seed, heads_total=self.Hkv_full, tp=tp)
         for i, layer in enumerate(model.model.layers):
             at, mlp = layer.self_attn, layer.mlp
@@ -99,6 +106,8 @@ class FastGearDecoder:
             self.layers.append(dict(
                 wqkv=wqkv.contiguous(), wqkv_full=wqkv_full if tp_world > 1 else None, wo=at.o_proj.weight, wgu=wgu.contiguous(), wd=mlp.down_proj.weight,
                 cache=(Fp16KVCache(batch, self.Hkv, max_tokens, dev, self.D) if cache_kind == "fp16" else
+                       KiviKVCache(batch, self.Hkv, max_tokens, at.k_bits, at.group_size, at.residual_length, dev, self.D)
+                       if cache_kind == "kivi" else
                        GearKVCache(batch, self.Hkv, max_tokens, at.compress_config, dev, self.D, seed=seed + i,
                                    pool=self.pool, layer=i, heads_total=self.Hkv_full, tp=tp)),
                 rotary=at.rotary_emb))
@@ -203,6 +212,10 @@ class FastGearDecoder:
         dyn: position / slot come from the device state (graph replay)."""
         cache = lw["cache"]
         B, K = res.shape
+        if self.cache_kind == "kivi":
+            # the projection (one fused launch for B <= 4), then gear_kivi_rope_append: RoPE, K window, V ring and the evicted
+            # V row's codes in one launch
+            return cache.append_rope(self._norm_linear(res, lw["wqkv"]), self.Hq, self.pos, self.theta)
         if self._fused(B, K):
             if not dyn and cache.n_win >= cache.R:
                 raise L.GearError(f"FastGearDecoder: the cache window is full ({cache.n_win} of {cache.R} slots): capacity reached")
@@ -271,6 +284,11 @@ class FastGearDecoder:
         self.pos = sv["pos"]
         self._state_dirty = True
 
+    def _kivi_refused(self, what):
+        if self.cache_kind == "kivi":
+            raise NotImplementedError(f"{what}: not implemented for the KIVI cache (cache_kind='kivi'): it has prefill(), eager "
+                                      "step() and generate() only")
+
     def _shared_refused(self, what, hint=""):
         if self.shared_live:
             raise NotImplementedError(f"{what}: not implemented while a shared prefix is live (shared-prefix decoding has eager "
@@ -334,6 +352,7 @@ class FastGearDecoder:
         capacity is refused before anything changes."""
         from .cache import N_MAX_EXTEND, _check_room
         self._shared_refused("extend()", ": use extend_shared()")
+        self._kivi_refused("extend()")
         if self.tp_world > 1:
             raise NotImplementedError("extend(): head-sharded (tp_world > 1) chunk extend is not implemented -- use step()")
         if torch.cuda.is_current_stream_capturing():
@@ -418,6 +437,7 @@ class FastGearDecoder:
         layer's n post-RoPE K / V rows are kept until accept(m) commits rows 0 .. m - 1.  Changes no cache state."""
         from .cache import N_MAX_VERIFY, _check_room
         self._shared_refused("verify()")
+        self._kivi_refused("verify()")
         if self.tp_world > 1:
             raise NotImplementedError("verify(): head-sharded (tp_world > 1) verification is not implemented -- use step()")
         if torch.cuda.is_current_stream_capturing():
@@ -463,6 +483,7 @@ class FastGearDecoder:
         """Commit rows 0 .. m - 1 (0 <= m <= n) of the last verify() to every layer's cache, exactly as extend() of those tokens
         commits them (the windows fill, the pooled block compressor runs at each boundary); advances pos.  Returns m."""
         self._shared_refused("accept()")
+        self._kivi_refused("accept()")
         p = getattr(self, "_pending", None)
         if p is None or p["pos"] != self.pos:
             raise ValueError("accept(): no pending verify() (each verify() can be accepted once, before any other step)")
@@ -493,6 +514,7 @@ class FastGearDecoder:
         from .cache import N_MAX_VERIFY, _check_room
         from .speculative import tree_layout
         self._shared_refused("verify_tree()")
+        self._kivi_refused("verify_tree()")
         if self.tp_world > 1:
             raise NotImplementedError("verify_tree(): head-sharded (tp_world > 1) verification is not implemented -- use step()")
         if torch.cuda.is_current_stream_capturing():
@@ -545,6 +567,7 @@ class FastGearDecoder:
         gathered along the token axis and committed exactly as accept(m) commits rows 0 .. m - 1; advances pos.  Returns m.
         A verify_tree() is consumed by accept_path() only, a verify() by accept() only."""
         self._shared_refused("accept_path()")
+        self._kivi_refused("accept_path()")
         p = getattr(self, "_pending_tree", None)
         if getattr(self, "_pending", None) is not None:
             raise ValueError("accept_path(): the pending pass is a verify(): commit it with accept()")
@@ -623,6 +646,7 @@ class FastGearDecoder:
         up to tree_width continuations of the trailing n-gram under one root), checks it in one verify_tree() pass, walks it with
         speculative.tree_accept and commits the batch's minimum path length through accept_path(), each row its own path."""
         from .speculative import accepted_lengths, ngram_draft
+        self._kivi_refused("generate_speculative()")
         if self.shared_prefix_tokens:
             raise NotImplementedError("generate_speculative(): not implemented for a shared-prefix decoder (shared_prefix_tokens > 0)")
         if tree_width > 1:
@@ -695,6 +719,9 @@ class FastGearDecoder:
         if self.pool is not None and self.layers[0]["cache"].n_win == self.layers[0]["cache"].R:
             self.pool.compress_all()
             self._after_boundary()
+        elif self.cache_kind == "kivi":
+            for lw in self.layers:
+                lw["cache"].maybe_compress()      # the K window as one block, every `residual` tokens
         return self._norm_linear(res, self.w_head)
 
     # ------------------------------------------------------------------------------------------------ beam search
@@ -703,6 +730,7 @@ class FastGearDecoder:
         the batch axis in place, in one call (GearKVCachePool.reorder -> gear_cache_reorder).  src_idx: int32 / int64 device tensor
         [batch] (read on the device), a CPU tensor or a list.  With a shared prefix only the tails move -- the prefix pool is
         untouched; on a plain decoder the whole cache moves, prompt segment included (correct, only expensive)."""
+        self._kivi_refused("reorder()")
         if self.tp_world > 1:
             raise NotImplementedError("reorder(): not implemented for head-sharded decoders (tp_world > 1)")
         if self.pool is None:
@@ -712,6 +740,7 @@ class FastGearDecoder:
 
     # ------------------------------------------------------------------------------------------------ snapshots
     def _snapshot_refused(self, what):
+        self._kivi_refused(what)
         if self.tp_world > 1:
             raise NotImplementedError(f"{what}: not implemented for head-sharded decoders (tp_world > 1)")
         if self.pool is None:
@@ -848,6 +877,7 @@ class FastGearDecoder:
         if self.shared_prefix_tokens:
             raise NotImplementedError("step_graph(): not implemented for a shared-prefix decoder (shared_prefix_tokens > 0): the "
                                       "shared-prefix attention has eager steps only")
+        self._kivi_refused("step_graph()")
         if self.pool is None:
             raise NotImplementedError("step_graph(): the fp16-cache baseline has eager steps only")
         if self.gather is not None and not self.gather.capturable and not getattr(self, "_peer_tried", False):
@@ -921,6 +951,8 @@ class FastGearDecoder:
         input_ids must be the stored prompt (ValueError otherwise)."""
         if shared_prefix and graph:
             raise NotImplementedError("generate(shared_prefix=True, graph=True): shared-prefix decoding has eager steps only")
+        if graph or shared_prefix:
+            self._kivi_refused("generate(graph=True)" if graph else "generate(shared_prefix=True)")
         if (suffix_ids is not None or reuse_prefix) and not shared_prefix:
             raise ValueError("generate(): suffix_ids / reuse_prefix need shared_prefix=True")
         if sampling is not None:

@@ -8,7 +8,7 @@ shrink the model, --all to run the three variants back to back.  There is no net
 the prompt is synthetic token ids, which does not change the timing of a greedy decode.
 
     python harness.py --model gearl --batch_size 8            # the reference's default run
-    python harness.py --all --batch_size 1 --fast             # all variants; GEAR also through the fast decode path
+    python harness.py --all --batch_size 1 --fast             # all three variants through the fast decode path
 """
 import argparse
 import json
@@ -119,6 +119,14 @@ def run(variant, args, dev):
         from gear_amd.fast_decode import FastGearDecoder
         out = FastGearDecoder(model, args.max_length + 8, batch=args.batch_size, cache_kind="fp16").generate(ids, args.max_length,
                                                                                                              **fast_kw)
+    elif variant == "KIVI" and args.fast:
+        # the KIVI baseline through the SAME decoder too (cache.KiviKVCache on csrc/kivi.hip): the three rows differ in the cache only
+        from gear_amd.fast_decode import FastGearDecoder
+        dec = FastGearDecoder(model, args.max_length + 8, batch=args.batch_size, cache_kind="kivi")
+        out = dec.generate(ids, args.max_length, **fast_kw)
+        cache_bytes = sum(t.numel() * t.element_size() for lw in dec.layers for t in vars(lw["cache"]).values()
+                          if isinstance(t, torch.Tensor) and t.dim() == 4)
+        del dec
     else:
         out = model.generate(ids, args.max_length, **hook_kw)
     torch.cuda.synchronize()
@@ -126,13 +134,13 @@ def run(variant, args, dev):
     peak = torch.cuda.max_memory_allocated(dev) / 2 ** 20
     beams = args.num_beams if variant == "gearl" and args.num_beams else 0
     new = (out.shape[1] - args.prompt_len) * (beams or args.batch_size)
-    print(f"[{variant}{' (fast path)' if variant in ('gearl', 'None') and args.fast else ''}] Peak memory usage on GPU: {peak:.1f} MB")
+    print(f"[{variant}{' (fast path)' if args.fast else ''}] Peak memory usage on GPU: {peak:.1f} MB")
     if cache_bytes is not None:
         print(f"[{variant}] allocated cache: {cache_bytes / 2 ** 20:.1f} MB{' (shared prefix)' if args.shared_prefix else ''}")
     print(f"[{variant}] time {dt:.3f}   ({new / dt:.1f} new tokens/s, {f'{beams} beams' if beams else f'batch {args.batch_size}'}, prompt {args.prompt_len} -> {out.shape[1]})")
     del model
     torch.cuda.empty_cache()
-    return dict(variant=variant, fast=bool(args.fast and variant in ("gearl", "None")), batch_size=args.batch_size, prompt_len=args.prompt_len,
+    return dict(variant=variant, fast=bool(args.fast), batch_size=args.batch_size, prompt_len=args.prompt_len,
                 max_length=int(out.shape[1]), time_s=dt, new_tokens_per_s=new / dt, peak_mem_MiB=peak, layers=args.layers,
                 **(dict(cache_bytes=cache_bytes) if cache_bytes is not None else {}),
                 **(dict(shared_prefix=True) if args.shared_prefix and variant == "gearl" else {}),
@@ -156,7 +164,7 @@ def main():
     ap.add_argument("--loop", type=int, default=3)
     ap.add_argument("--left", type=float, default=0.0, help="outlier fraction (fast path only: the hook's fused path stores none)")
     ap.add_argument("--layers", type=int, default=32)
-    ap.add_argument("--fast", action="store_true", help="GEAR through FastGearDecoder (pre-allocated cache, fused kernels)")
+    ap.add_argument("--fast", action="store_true", help="every variant through FastGearDecoder (pre-allocated cache, fused kernels): cache kinds gear / kivi / fp16")
     ap.add_argument("--shared_prefix", action="store_true",
                     help="with --fast: the batch continues ONE prompt stored once (shared-prefix decoding) instead of batch_size copies")
     ap.add_argument("--num_beams", type=int, default=0,

@@ -627,6 +627,35 @@ int gear_xchg_close(void* ptr);
 int gear_xchg_allgather(const void* src, int rows, size_t row_bytes, int world, int rank, const void* peers, void* out,
                         void* status, void* stream);
 
+/* ---- the KIVI cache on the fused decode path (csrc/kivi.hip) ---------------------------------------------------------------------
+ * The KIVI baseline's state machine (K: an fp16 window quantized per channel as one block of R tokens; V: a sliding fp16 window whose
+ * oldest token is quantized per token) on a pre-allocated cache.  A gear_cache_view describes it: kcode / kscale / kmn and vcode /
+ * vscale / vmn with the layouts of the streaming cache (no factors, no outlier lists: rk = rv = kv = kk_cap = 0), wcap = R, kwin =
+ * the K window fp16 [B*Hkv, R, 128] (token t >= Tk in row t - Tk) and vwin = the V RING fp16 [B*Hkv, R + 1, 128]: token t lives in
+ * row t % (R + 1), so the row token n overwrites holds token n - (R + 1).  bits 2 / 4, group 64, R 64 / 128, mode 0.
+ *
+ * gear_kivi_rope_append: gear_rope_append for this cache -- qkv fp16 [B, (Hq + 2 Hkv) * 128] -> RoPE at `pos` on q and k, q to
+ *   q_out [B, Hq, 128], k into row kslot of the K window, v into ring row n % (R + 1) (n = the token's index in the sequence).
+ *   evict_row = n - (R + 1): in the same launch, before the overwrite, the ring row's old contents (token n - (R + 1)) are
+ *   quantized per token (groups of 64 channels, fp16 scale and minimum, gear_quant_pack_lastdim's fp16-stepwise arithmetic) into
+ *   row evict_row of vcode / vscale / vmn [B*Hkv, tcap, ...]; evict_row = -1: nothing is evicted (the ring is not full yet, or
+ *   the prompt's prefill packed that row already).  One launch.
+ * gear_kivi_append: the same for rows that are already rotated, k_new / v_new fp16 [B, Hkv, 128].
+ * gear_attn_decode_kivi: q fp16 [B, Hq, 128] -> out fp16 [B, Hq, 128] (lse optional float [B, Hq]): ONE fp32 softmax over the L
+ *   tokens -- K from the codes for [0, Tk) and from the window for [Tk, L), V from the codes for [0, Nv) and from the ring for
+ *   [Nv, L).  Tk % R == 0, 0 <= L - Tk <= R, 0 <= L - Nv <= R + 1, Nv rounded down to 64 must not exceed Tk.  The whole 64-token
+ *   chunks below Nv go through the decode partial dispatch, one seam kernel per output row scores the remaining <= 63 + R + 1
+ *   tokens and merges: two launches (one when Nv < 64), whatever L is.  No cache state changes; the same call on the same data
+ *   gives the same bits.  workspace: gear_attn_decode_kivi_workspace(B, Hq, T, bits) bytes for any T >= Nv (0: bad arguments). */
+int gear_kivi_rope_append(const void* qkv, int B, int Hq, int Hkv, int D, int pos, float theta, void* q_out, void* kwin, int kslot,
+                          void* vring, int n, int R, int evict_row, void* vcode, void* vscale, void* vmn, int tcap, int group,
+                          int bits, void* stream);
+int gear_kivi_append(const void* k_new, const void* v_new, int B, int Hkv, int D, void* kwin, int kslot, void* vring, int n, int R,
+                     int evict_row, void* vcode, void* vscale, void* vmn, int tcap, int group, int bits, void* stream);
+size_t gear_attn_decode_kivi_workspace(int B, int Hq, int T, int bits);
+int gear_attn_decode_kivi(const gear_cache_view* c, const void* q, int Hq, int L, int Tk, int Nv, float qscale, void* out, void* lse,
+                          void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
