@@ -103,6 +103,13 @@ SIGNATURES = {
     "gear_kivi_append": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "gear_attn_decode_kivi_workspace": (_sz, [_i, _i, _i, _i]),
     "gear_attn_decode_kivi": (_i, [_vp, _vp, _i, _i, _i, _i, C.c_float, _vp, _vp, _vp, _sz, _vp]),
+    # rope_scaling: the parents' argument lists with `float theta` -> `const float* inv_freq, float attn_factor`
+    "gear_rope_append_freq": (_i, [_vp, _i, _i, _i, _i, _i, _vp, C.c_float, _vp, _vp, _vp, _i, _i, _vp]),
+    "gear_rope_append_dyn_freq": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, C.c_float, _vp, _vp, _vp, _i, _vp]),
+    "gear_gemv_qkv_rope_freq": (_i, [_vp, _vp, _vp, C.c_float, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, C.c_float, _vp,
+                                     _vp, _vp, _vp, _vp, _vp]),
+    "gear_kivi_rope_append_freq": (_i, [_vp, _i, _i, _i, _i, _i, _vp, C.c_float, _vp, _vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _i,
+                                        _i, _i, _vp]),
 }
 
 ABI_VERSION = 5      # what this table was written against (gear_abi_version() of the library must match)

@@ -300,6 +300,28 @@ N_MAX_EXTEND = 2048      # query tokens per gear_attn_extend_cache call
 N_MAX_VERIFY = 16        # query tokens per gear_attn_verify_cache call
 
 
+def _rope_table(rope, like):
+    """rope = (inv_freq, attn_factor) of a scaled model (gear_amd/rope.py): the table must be 64 fp32 values on the tensors' device."""
+    inv_freq, attn_factor = rope
+    if inv_freq.dtype != torch.float32 or inv_freq.numel() != 64 or inv_freq.device != like.device or not inv_freq.is_contiguous():
+        raise L.GearError(f"rope table: 64 contiguous float32 values on {like.device} expected, got {list(inv_freq.shape)} "
+                          f"{inv_freq.dtype} on {inv_freq.device}")
+    return inv_freq, float(attn_factor)
+
+
+def _rope_append(qkv, B, Hq, Hkv, D, pos, theta, rope, q, kwin, vwin, slot, W):
+    """gear_rope_append, or its table flavour when `rope` is given."""
+    if rope is None:
+        rc = L.load().gear_rope_append(L.ptr(qkv), B, Hq, Hkv, D, pos, theta, L.ptr(q), L.ptr(kwin), L.ptr(vwin), slot, W,
+                                       L.stream_ptr(qkv))
+        L.check(rc, "gear_rope_append")
+        return
+    inv_freq, attn_factor = _rope_table(rope, qkv)
+    rc = L.load().gear_rope_append_freq(L.ptr(qkv), B, Hq, Hkv, D, pos, L.ptr(inv_freq), attn_factor, L.ptr(q), L.ptr(kwin),
+                                        L.ptr(vwin), slot, W, L.stream_ptr(qkv))
+    L.check(rc, "gear_rope_append_freq")
+
+
 def _check_rows(k, v, B, H, D, n):
     want = (B, H, n, D)
     if tuple(k.shape) != want or tuple(v.shape) != want or k.dtype != torch.float16 or v.dtype != torch.float16:
@@ -562,12 +584,11 @@ class GearKVCache:
             self.kwin[:, :, :self.n_win] = k[:, :, nq:]
             self.vwin[:, :, :self.n_win] = v[:, :, nq:]
 
-    def append_rope(self, qkv: torch.Tensor, n_q_heads: int, pos: int, theta: float) -> torch.Tensor:
-        """qkv fp16 [B, (Hq + 2 Hkv) * 128] of the new token -> RoPE, k / v into the window; returns q [B,Hq,1,128]."""
+    def append_rope(self, qkv: torch.Tensor, n_q_heads: int, pos: int, theta: float, rope=None) -> torch.Tensor:
+        """qkv fp16 [B, (Hq + 2 Hkv) * 128] of the new token -> RoPE, k / v into the window; returns q [B,Hq,1,128].
+        rope = (inv_freq fp32 device tensor [64], attn_factor): the frequencies of a scaled model (gear_amd/rope.py) instead of theta."""
         q = torch.empty((self.B, n_q_heads, 1, self.D), dtype=torch.float16, device=qkv.device)
-        rc = L.load().gear_rope_append(L.ptr(qkv), self.B, n_q_heads, self.H, self.D, pos, theta, L.ptr(q), L.ptr(self.kwin),
-                                       L.ptr(self.vwin), self.n_win, self.R, L.stream_ptr(qkv))
-        L.check(rc, "gear_rope_append")
+        _rope_append(qkv, self.B, n_q_heads, self.H, self.D, pos, theta, rope, q, self.kwin, self.vwin, self.n_win, self.R)
         self.n_win += 1
         return q
 
@@ -606,11 +627,18 @@ class GearKVCache:
         return self._attend(q, self.n_comp, self.n_win, None, return_lse)
 
     # ---- device-state variants: no host-side counters change here (a captured graph replays these launches) ----------
-    def append_rope_dyn(self, qkv: torch.Tensor, n_q_heads: int, theta: float) -> torch.Tensor:
+    def append_rope_dyn(self, qkv: torch.Tensor, n_q_heads: int, theta: float, rope=None) -> torch.Tensor:
         q = torch.empty((self.B, n_q_heads, 1, self.D), dtype=torch.float16, device=qkv.device)
-        rc = L.load().gear_rope_append_dyn(L.ptr(qkv), self.B, n_q_heads, self.H, self.D, L.ptr(self.state), theta, L.ptr(q),
-                                           L.ptr(self.kwin), L.ptr(self.vwin), self.R, L.stream_ptr(qkv))
-        L.check(rc, "gear_rope_append_dyn")
+        if rope is None:
+            rc = L.load().gear_rope_append_dyn(L.ptr(qkv), self.B, n_q_heads, self.H, self.D, L.ptr(self.state), theta, L.ptr(q),
+                                               L.ptr(self.kwin), L.ptr(self.vwin), self.R, L.stream_ptr(qkv))
+            L.check(rc, "gear_rope_append_dyn")
+        else:
+            inv_freq, attn_factor = _rope_table(rope, qkv)
+            rc = L.load().gear_rope_append_dyn_freq(L.ptr(qkv), self.B, n_q_heads, self.H, self.D, L.ptr(self.state), L.ptr(inv_freq),
+                                                    attn_factor, L.ptr(q), L.ptr(self.kwin), L.ptr(self.vwin), self.R,
+                                                    L.stream_ptr(qkv))
+            L.check(rc, "gear_rope_append_dyn_freq")
         return q
 
     def attend_dyn(self, q: torch.Tensor) -> torch.Tensor:
@@ -861,13 +889,11 @@ class Fp16KVCache:
         self.vwin[:, :, :T] = v
         self.n_win = T
 
-    def append_rope(self, qkv: torch.Tensor, n_q_heads: int, pos: int, theta: float) -> torch.Tensor:
+    def append_rope(self, qkv: torch.Tensor, n_q_heads: int, pos: int, theta: float, rope=None) -> torch.Tensor:
         if self.n_win >= self.R:
             raise L.GearError(f"Fp16KVCache: capacity {self.R} reached")
         q = torch.empty((self.B, n_q_heads, 1, self.D), dtype=torch.float16, device=qkv.device)
-        rc = L.load().gear_rope_append(L.ptr(qkv), self.B, n_q_heads, self.H, self.D, pos, theta, L.ptr(q), L.ptr(self.kwin),
-                                       L.ptr(self.vwin), self.n_win, self.R, L.stream_ptr(qkv))
-        L.check(rc, "gear_rope_append")
+        _rope_append(qkv, self.B, n_q_heads, self.H, self.D, pos, theta, rope, q, self.kwin, self.vwin, self.n_win, self.R)
         self.n_win += 1
         return q
 
@@ -1068,17 +1094,23 @@ class KiviKVCache:
             self.n_vpacked = row + 1
         self.n_tok += 1
 
-    def append_rope(self, qkv: torch.Tensor, n_q_heads: int, pos: int, theta: float) -> torch.Tensor:
+    def append_rope(self, qkv: torch.Tensor, n_q_heads: int, pos: int, theta: float, rope=None) -> torch.Tensor:
         """qkv fp16 [B, (Hq + 2 Hkv) * 128] of the new token -> RoPE, k into the K window, v into the ring (its evicted row
-        quantized in the same launch); returns q [B, Hq, 1, 128]."""
+        quantized in the same launch); returns q [B, Hq, 1, 128].  rope = (inv_freq device tensor [64], attn_factor): a scaled
+        model's frequencies instead of theta."""
         L.require_gpu(qkv)
         row = self._evict_row()
         q = torch.empty((self.B, n_q_heads, 1, self.D), dtype=torch.float16, device=qkv.device)
-        rc = L.load().gear_kivi_rope_append(L.ptr(qkv), self.B, n_q_heads, self.H, self.D, pos, theta, L.ptr(q), L.ptr(self.kwin),
-                                            self.n_kwin, L.ptr(self.vring), self.n_tok, self.R, row, L.ptr(self.vcode),
-                                            L.ptr(self.vscale), L.ptr(self.vmn), self.Tmax, self.group, self.bits,
-                                            L.stream_ptr(qkv))
-        L.check(rc, "gear_kivi_rope_append")
+        tail = (L.ptr(q), L.ptr(self.kwin), self.n_kwin, L.ptr(self.vring), self.n_tok, self.R, row, L.ptr(self.vcode),
+                L.ptr(self.vscale), L.ptr(self.vmn), self.Tmax, self.group, self.bits, L.stream_ptr(qkv))
+        if rope is None:
+            rc = L.load().gear_kivi_rope_append(L.ptr(qkv), self.B, n_q_heads, self.H, self.D, pos, theta, *tail)
+            L.check(rc, "gear_kivi_rope_append")
+        else:
+            inv_freq, attn_factor = _rope_table(rope, qkv)
+            rc = L.load().gear_kivi_rope_append_freq(L.ptr(qkv), self.B, n_q_heads, self.H, self.D, pos, L.ptr(inv_freq), attn_factor,
+                                                     *tail)
+            L.check(rc, "gear_kivi_rope_append_freq")
         self._appended(row)
         return q
 

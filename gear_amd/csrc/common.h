@@ -95,6 +95,33 @@ __device__ __forceinline__ uint32_t f2h2_bits(float lo, float hi) {
     return r;
 }
 
+// cos / sin of rotation pair p at position pos, rounded to fp16 (HF computes them in fp32 and casts): the one place the RoPE
+// kernels (decode_ops.hip, gemv_f16.hip, kivi.hip) take their angle from.  TAB = false: inv_freq = theta^(-2p/128) from
+// log2(theta).  TAB = true (rope_scaling: linear / llama3 / yarn): inv_freq from a 64-entry device table, cos / sin times the
+// attention factor in fp32 before the cast, as transformers does.
+template <bool TAB>
+__device__ __forceinline__ void rope_cos_sin(int p, int pos, float log2_theta, const float* __restrict__ inv_tab, float attn_factor,
+                                             float& c, float& sn) {
+    if constexpr (TAB) {
+        const float ang = (float)pos * inv_tab[p];
+        c = hround(cosf(ang) * attn_factor);
+        sn = hround(sinf(ang) * attn_factor);
+    } else {
+        const float inv_freq = exp2f(-(float)(2 * p) / 128.0f * log2_theta);
+        const float ang = (float)pos * inv_freq;
+        c = hround(cosf(ang));
+        sn = hround(sinf(ang));
+    }
+}
+
+// argument checks the table flavours (gear_*_freq) add to their parents'
+#define GEAR_CHECK_ROPE_TABLE(fn, inv_freq, attn_factor)                                                                     \
+    do {                                                                                                                     \
+        GEAR_CHECK_ARG((inv_freq) != nullptr, "%s: null inv_freq table", fn);                                                \
+        GEAR_CHECK_ARG((attn_factor) > 0.0f && (attn_factor) <= 3.0e38f, "%s: attn_factor must be positive and finite (got %g)", fn, \
+                       (double)(attn_factor));                                                                               \
+    } while (0)
+
 // IEEE-correct fp32 division (never the v_rcp approximation): torch semantics
 __device__ __forceinline__ float div_rn(float a, float b) { return __fdiv_rn(a, b); }
 

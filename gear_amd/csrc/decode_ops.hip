@@ -11,11 +11,13 @@
 
 namespace {
 
-// qkv: [B, (Hq + 2 Hkv) * 128] = [q heads | k heads | v heads]
+// qkv: [B, (Hq + 2 Hkv) * 128] = [q heads | k heads | v heads].  TAB: the frequencies come from inv_tab (rope_scaling), not theta
+template <bool TAB>
 __global__ __launch_bounds__(256) void rope_append_kernel(const uint16_t* __restrict__ qkv, int B, int Hq, int Hkv, int pos,
                                                           float log2_theta, uint16_t* __restrict__ q_out,
                                                           uint16_t* __restrict__ kwin, uint16_t* __restrict__ vwin,
-                                                          int slot, int W, const int* __restrict__ dyn) {
+                                                          int slot, int W, const int* __restrict__ dyn,
+                                                          const float* __restrict__ inv_tab, float attn_factor) {
     if (dyn) { pos = dyn[0]; slot = dyn[1]; }   // device-side state {pos, slot, T, W} (hipGraph replay)
     const int HT = Hq + 2 * Hkv;
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;  // one thread per (b, head, pair index 0..63)
@@ -32,9 +34,8 @@ __global__ __launch_bounds__(256) void rope_append_kernel(const uint16_t* __rest
         return;
     }
     // inv_freq = theta^(-2p/128); HF computes cos/sin in fp32 and casts them to fp16
-    const float inv_freq = exp2f(-(float)(2 * p) / 128.0f * log2_theta);
-    const float ang = (float)pos * inv_freq;
-    const float c = hround(cosf(ang)), sn = hround(sinf(ang));
+    float c, sn;
+    rope_cos_sin<TAB>(p, pos, log2_theta, inv_tab, attn_factor, c, sn);
     const float x1 = h2f_bits(src[p]), x2 = h2f_bits(src[p + 64]);
     const float lo = hround(hround(x1 * c) + hround(-x2 * sn));   // q*cos + rotate_half(q)*sin, fp16 op by op
     const float hi = hround(hround(x2 * c) + hround(x1 * sn));
@@ -101,29 +102,52 @@ __global__ __launch_bounds__(256) void silu_mul_kernel(const uint16_t* __restric
 
 }  // namespace
 
+// the four entry points differ in where position / slot (arguments or the device state) and the frequencies (theta or a table) come from
+static int rope_append_launch(const char* fn, const void* qkv, int B, int Hq, int Hkv, int D, int pos, float theta,
+                              const float* inv_freq, float attn_factor, void* q_out, void* kwin, void* vwin, int slot, int W,
+                              const void* dyn_state, bool dyn, void* stream) {
+    GEAR_CHECK_ARG(D == 128, "%s: head_dim must be 128 (got %d)", fn, D);
+    GEAR_CHECK_ARG(qkv && q_out && kwin && vwin && (!dyn || dyn_state), "%s: null pointer", fn);
+    GEAR_CHECK_ARG(dyn || (B > 0 && Hq > 0 && Hkv > 0 && slot >= 0 && slot < W && pos >= 0), "%s: bad arguments", fn);
+    const int64_t n = (int64_t)B * (Hq + 2 * Hkv) * 64;
+    const dim3 grid((unsigned)((n + 255) / 256));
+    if (inv_freq)
+        hipLaunchKernelGGL(rope_append_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, (const uint16_t*)qkv, B, Hq, Hkv, pos,
+                           0.0f, (uint16_t*)q_out, (uint16_t*)kwin, (uint16_t*)vwin, slot, W, (const int*)dyn_state, inv_freq,
+                           attn_factor);
+    else
+        hipLaunchKernelGGL(rope_append_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, (const uint16_t*)qkv, B, Hq, Hkv, pos,
+                           log2f(theta), (uint16_t*)q_out, (uint16_t*)kwin, (uint16_t*)vwin, slot, W, (const int*)dyn_state,
+                           (const float*)nullptr, 1.0f);
+    GEAR_CHECK_LAUNCH(fn);
+    return 0;
+}
+
 extern "C" int gear_rope_append(const void* qkv, int B, int Hq, int Hkv, int D, int pos, float theta, void* q_out,
                                 void* kwin, void* vwin, int slot, int W, void* stream) {
-    GEAR_CHECK_ARG(D == 128, "gear_rope_append: head_dim must be 128 (got %d)", D);
-    GEAR_CHECK_ARG(qkv && q_out && kwin && vwin, "gear_rope_append: null pointer");
-    GEAR_CHECK_ARG(B > 0 && Hq > 0 && Hkv > 0 && slot >= 0 && slot < W && pos >= 0, "gear_rope_append: bad arguments");
-    const int64_t n = (int64_t)B * (Hq + 2 * Hkv) * 64;
-    hipLaunchKernelGGL(rope_append_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       (const uint16_t*)qkv, B, Hq, Hkv, pos, log2f(theta), (uint16_t*)q_out, (uint16_t*)kwin, (uint16_t*)vwin,
-                       slot, W, (const int*)nullptr);
-    GEAR_CHECK_LAUNCH("gear_rope_append");
-    return 0;
+    return rope_append_launch("gear_rope_append", qkv, B, Hq, Hkv, D, pos, theta, nullptr, 1.0f, q_out, kwin, vwin, slot, W, nullptr,
+                              false, stream);
+}
+
+extern "C" int gear_rope_append_freq(const void* qkv, int B, int Hq, int Hkv, int D, int pos, const float* inv_freq,
+                                     float attn_factor, void* q_out, void* kwin, void* vwin, int slot, int W, void* stream) {
+    GEAR_CHECK_ROPE_TABLE("gear_rope_append_freq", inv_freq, attn_factor);
+    return rope_append_launch("gear_rope_append_freq", qkv, B, Hq, Hkv, D, pos, 0.0f, inv_freq, attn_factor, q_out, kwin, vwin, slot,
+                              W, nullptr, false, stream);
 }
 
 extern "C" int gear_rope_append_dyn(const void* qkv, int B, int Hq, int Hkv, int D, const void* dyn_state, float theta,
                                     void* q_out, void* kwin, void* vwin, int W, void* stream) {
-    GEAR_CHECK_ARG(D == 128, "gear_rope_append_dyn: head_dim must be 128 (got %d)", D);
-    GEAR_CHECK_ARG(qkv && q_out && kwin && vwin && dyn_state, "gear_rope_append_dyn: null pointer");
-    const int64_t n = (int64_t)B * (Hq + 2 * Hkv) * 64;
-    hipLaunchKernelGGL(rope_append_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       (const uint16_t*)qkv, B, Hq, Hkv, 0, log2f(theta), (uint16_t*)q_out, (uint16_t*)kwin, (uint16_t*)vwin,
-                       0, W, (const int*)dyn_state);
-    GEAR_CHECK_LAUNCH("gear_rope_append_dyn");
-    return 0;
+    return rope_append_launch("gear_rope_append_dyn", qkv, B, Hq, Hkv, D, 0, theta, nullptr, 1.0f, q_out, kwin, vwin, 0, W, dyn_state,
+                              true, stream);
+}
+
+extern "C" int gear_rope_append_dyn_freq(const void* qkv, int B, int Hq, int Hkv, int D, const void* dyn_state,
+                                         const float* inv_freq, float attn_factor, void* q_out, void* kwin, void* vwin, int W,
+                                         void* stream) {
+    GEAR_CHECK_ROPE_TABLE("gear_rope_append_dyn_freq", inv_freq, attn_factor);
+    return rope_append_launch("gear_rope_append_dyn_freq", qkv, B, Hq, Hkv, D, 0, 0.0f, inv_freq, attn_factor, q_out, kwin, vwin, 0,
+                              W, dyn_state, true, stream);
 }
 
 __global__ void decode_state_advance_kernel(int* st) {  // one token appended: pos, slot and W move on

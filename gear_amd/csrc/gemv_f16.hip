@@ -66,9 +66,11 @@ struct GemvArgs {
     const int* dyn;
     uint16_t *q_out, *kwin, *vwin;
     int half_n;               // EPI_SWIGLU with BLOCKED weights [gate rows | up rows]: N / 2 (0: the rows are interleaved gate, up, gate, ...)
+    const float* inv_tab;     // EPI_ROPE, TAB: 64 inverse frequencies (rope_scaling) in place of log2_theta
+    float attn_factor;        // EPI_ROPE, TAB: cos / sin scale
 };
 
-template <int NB, int SK, int NORM, int EPI>
+template <int NB, int SK, int NORM, int EPI, bool TAB = false>
 __global__ __launch_bounds__(EPI == EPI_ROPE ? 256 * SK : 256) void gemv_tok_kernel(GemvArgs a) {
     constexpr int WPB = EPI == EPI_ROPE ? 4 * SK : 4;   // waves per block (RoPE blocks always hold 4 rows)
     constexpr int RPB = WPB / SK;                       // rows per block
@@ -171,9 +173,8 @@ __global__ __launch_bounds__(EPI == EPI_ROPE ? 256 * SK : 256) void gemv_tok_ker
             } else {   // same arithmetic as rope_append_kernel
                 uint16_t* dst = (head < Hq) ? a.q_out + ((int64_t)b * Hq + head) * 128
                                             : a.kwin + (((int64_t)b * Hkv + (head - Hq)) * a.wcap + slot) * 128;
-                const float inv_freq = exp2f(-(float)(2 * p) / 128.0f * a.log2_theta);
-                const float ang = (float)pos * inv_freq;
-                const float c = hround(cosf(ang)), sn = hround(sinf(ang));
+                float c, sn;
+                rope_cos_sin<TAB>(p, pos, a.log2_theta, a.inv_tab, a.attn_factor, c, sn);
                 dst[p] = f2h_bits(hround(hround(x1 * c) + hround(-x2 * sn)));
                 dst[p + 64] = f2h_bits(hround(hround(x2 * c) + hround(x1 * sn)));
             }
@@ -181,13 +182,13 @@ __global__ __launch_bounds__(EPI == EPI_ROPE ? 256 * SK : 256) void gemv_tok_ker
     }
 }
 
-template <int SK, int NORM, int EPI>
+template <int SK, int NORM, int EPI, bool TAB = false>
 void launch_nb(int B, unsigned blocks, hipStream_t st, const GemvArgs& a) {
     dim3 grid(blocks), block(EPI == EPI_ROPE ? 256 * SK : 256);
-    if (B == 1) hipLaunchKernelGGL((gemv_tok_kernel<1, SK, NORM, EPI>), grid, block, 0, st, a);
-    else if (B == 2) hipLaunchKernelGGL((gemv_tok_kernel<2, SK, NORM, EPI>), grid, block, 0, st, a);
-    else if (B == 3) hipLaunchKernelGGL((gemv_tok_kernel<3, SK, NORM, EPI>), grid, block, 0, st, a);
-    else hipLaunchKernelGGL((gemv_tok_kernel<4, SK, NORM, EPI>), grid, block, 0, st, a);
+    if (B == 1) hipLaunchKernelGGL((gemv_tok_kernel<1, SK, NORM, EPI, TAB>), grid, block, 0, st, a);
+    else if (B == 2) hipLaunchKernelGGL((gemv_tok_kernel<2, SK, NORM, EPI, TAB>), grid, block, 0, st, a);
+    else if (B == 3) hipLaunchKernelGGL((gemv_tok_kernel<3, SK, NORM, EPI, TAB>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((gemv_tok_kernel<4, SK, NORM, EPI, TAB>), grid, block, 0, st, a);
 }
 
 // K split over the waves of a block.  Measured (tools/exp_gemv.py, GB/s of weight bytes, qkv / o / gate-up / down / lm_head):
@@ -255,33 +256,54 @@ extern "C" int gear_gemv_f16_norm(const void* x, const void* delta, const void* 
     return 0;
 }
 
-extern "C" int gear_gemv_qkv_rope(const void* x, const void* delta, const void* norm_w, float eps, const void* Wqkv, int B,
-                                  int K, int Hq, int Hkv, int D, int pos, int slot, int wcap, float theta,
-                                  const void* dyn_state, void* res_out, void* q_out, void* kwin, void* vwin, void* stream) {
-    GEAR_CHECK_ARG(D == 128, "gear_gemv_qkv_rope: head_dim must be 128 (got %d)", D);
-    GEAR_CHECK_ARG(x && Wqkv && q_out && kwin && vwin, "gear_gemv_qkv_rope: null pointer");
-    GEAR_CHECK_ARG(B >= 1 && B <= 4, "gear_gemv_qkv_rope: batch must be in [1,4] (got %d)", B);
-    GEAR_CHECK_ARG(K > 0 && K % 8 == 0 && Hq > 0 && Hkv > 0, "gear_gemv_qkv_rope: bad shape");
-    GEAR_CHECK_ARG(dyn_state || (slot >= 0 && slot < wcap && pos >= 0), "gear_gemv_qkv_rope: bad pos / slot");
-    GEAR_CHECK_ARG(!delta || (res_out && res_out != x && res_out != delta),
-                   "gear_gemv_qkv_rope: the new residual needs its own buffer");
+namespace {
+
+template <bool TAB>
+int gemv_qkv_rope_launch(const char* fn, const void* x, const void* delta, const void* norm_w, float eps, const void* Wqkv, int B,
+                         int K, int Hq, int Hkv, int D, int pos, int slot, int wcap, float theta, const float* inv_freq,
+                         float attn_factor, const void* dyn_state, void* res_out, void* q_out, void* kwin, void* vwin, void* stream) {
+    GEAR_CHECK_ARG(D == 128, "%s: head_dim must be 128 (got %d)", fn, D);
+    GEAR_CHECK_ARG(x && Wqkv && q_out && kwin && vwin, "%s: null pointer", fn);
+    GEAR_CHECK_ARG(B >= 1 && B <= 4, "%s: batch must be in [1,4] (got %d)", fn, B);
+    GEAR_CHECK_ARG(K > 0 && K % 8 == 0 && Hq > 0 && Hkv > 0, "%s: bad shape", fn);
+    GEAR_CHECK_ARG(dyn_state || (slot >= 0 && slot < wcap && pos >= 0), "%s: bad pos / slot", fn);
+    GEAR_CHECK_ARG(!delta || (res_out && res_out != x && res_out != delta), "%s: the new residual needs its own buffer", fn);
     GemvArgs a = {};
     a.x = (const uint16_t*)x; a.delta = (const uint16_t*)delta; a.nw = (const uint16_t*)norm_w;
     a.res_out = delta ? (uint16_t*)res_out : nullptr;
     a.eps = eps; a.W = (const uint16_t*)Wqkv; a.K = K; a.N = (Hq + 2 * Hkv) * 128;
-    a.Hq = Hq; a.Hkv = Hkv; a.pos = pos; a.slot = slot; a.wcap = wcap; a.log2_theta = log2f(theta);
+    a.Hq = Hq; a.Hkv = Hkv; a.pos = pos; a.slot = slot; a.wcap = wcap; a.log2_theta = TAB ? 0.0f : log2f(theta);
+    a.inv_tab = inv_freq; a.attn_factor = attn_factor;
     a.dyn = (const int*)dyn_state; a.q_out = (uint16_t*)q_out; a.kwin = (uint16_t*)kwin; a.vwin = (uint16_t*)vwin;
     const unsigned blocks = (unsigned)((Hq + 2 * Hkv) * 32);
     const bool folded = !delta && !norm_w, nw_only = !delta && norm_w;
     if (pick_sk(K, a.N, 2) == 2) {
-        if (folded) launch_nb<2, 1, EPI_ROPE>(B, blocks, (hipStream_t)stream, a);
-        else if (nw_only) launch_nb<2, 3, EPI_ROPE>(B, blocks, (hipStream_t)stream, a);
-        else launch_nb<2, 2, EPI_ROPE>(B, blocks, (hipStream_t)stream, a);
+        if (folded) launch_nb<2, 1, EPI_ROPE, TAB>(B, blocks, (hipStream_t)stream, a);
+        else if (nw_only) launch_nb<2, 3, EPI_ROPE, TAB>(B, blocks, (hipStream_t)stream, a);
+        else launch_nb<2, 2, EPI_ROPE, TAB>(B, blocks, (hipStream_t)stream, a);
     } else {
-        if (folded) launch_nb<1, 1, EPI_ROPE>(B, blocks, (hipStream_t)stream, a);
-        else if (nw_only) launch_nb<1, 3, EPI_ROPE>(B, blocks, (hipStream_t)stream, a);
-        else launch_nb<1, 2, EPI_ROPE>(B, blocks, (hipStream_t)stream, a);
+        if (folded) launch_nb<1, 1, EPI_ROPE, TAB>(B, blocks, (hipStream_t)stream, a);
+        else if (nw_only) launch_nb<1, 3, EPI_ROPE, TAB>(B, blocks, (hipStream_t)stream, a);
+        else launch_nb<1, 2, EPI_ROPE, TAB>(B, blocks, (hipStream_t)stream, a);
     }
-    GEAR_CHECK_LAUNCH("gear_gemv_qkv_rope");
+    GEAR_CHECK_LAUNCH(fn);
     return 0;
+}
+
+}  // namespace
+
+extern "C" int gear_gemv_qkv_rope(const void* x, const void* delta, const void* norm_w, float eps, const void* Wqkv, int B,
+                                  int K, int Hq, int Hkv, int D, int pos, int slot, int wcap, float theta,
+                                  const void* dyn_state, void* res_out, void* q_out, void* kwin, void* vwin, void* stream) {
+    return gemv_qkv_rope_launch<false>("gear_gemv_qkv_rope", x, delta, norm_w, eps, Wqkv, B, K, Hq, Hkv, D, pos, slot, wcap, theta,
+                                       nullptr, 1.0f, dyn_state, res_out, q_out, kwin, vwin, stream);
+}
+
+extern "C" int gear_gemv_qkv_rope_freq(const void* x, const void* delta, const void* norm_w, float eps, const void* Wqkv, int B,
+                                       int K, int Hq, int Hkv, int D, int pos, int slot, int wcap, const float* inv_freq,
+                                       float attn_factor, const void* dyn_state, void* res_out, void* q_out, void* kwin,
+                                       void* vwin, void* stream) {
+    GEAR_CHECK_ROPE_TABLE("gear_gemv_qkv_rope_freq", inv_freq, attn_factor);
+    return gemv_qkv_rope_launch<true>("gear_gemv_qkv_rope_freq", x, delta, norm_w, eps, Wqkv, B, K, Hq, Hkv, D, pos, slot, wcap, 0.0f,
+                                      inv_freq, attn_factor, dyn_state, res_out, q_out, kwin, vwin, stream);
 }

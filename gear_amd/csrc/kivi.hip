@@ -27,6 +27,8 @@ struct KiviAppend {
     int64_t bstride;
     int B, Hq, Hkv, rope, pos;
     float log2_theta;
+    const float* inv_tab;                    // table flavour (rope_scaling): 64 inverse frequencies in place of log2_theta
+    float attn_factor;
     uint16_t *q_out, *kwin, *vring;
     int kslot, R, vslot;
     int evict_row;                           // row of vcode / vscale / vmn the ring row at vslot goes to (-1: nothing to evict)
@@ -35,7 +37,7 @@ struct KiviAppend {
     int tcap;
 };
 
-template <int BITS>
+template <int BITS, bool TAB>
 __global__ __launch_bounds__(256) void kivi_append_kernel(KiviAppend a) {
     constexpr int CPW = 32 / BITS, LEVELS = (1 << BITS) - 1;
     const int HT = a.Hq + 2 * a.Hkv;
@@ -96,9 +98,8 @@ __global__ __launch_bounds__(256) void kivi_append_kernel(KiviAppend a) {
         return;
     }
     // rope_append_kernel's arithmetic (decode_ops.hip): cos / sin in fp32 cast to fp16, every elementwise op rounded to fp16
-    const float inv_freq = exp2f(-(float)(2 * p) / 128.0f * a.log2_theta);
-    const float ang = (float)a.pos * inv_freq;
-    const float c = hround(cosf(ang)), sn = hround(sinf(ang));
+    float c, sn;
+    rope_cos_sin<TAB>(p, a.pos, a.log2_theta, a.inv_tab, a.attn_factor, c, sn);
     const float x1 = h2f_bits(src[p]), x2 = h2f_bits(src[p + 64]);
     dst[p] = f2h_bits(hround(hround(x1 * c) + hround(-x2 * sn)));
     dst[p + 64] = f2h_bits(hround(hround(x2 * c) + hround(x1 * sn)));
@@ -122,8 +123,13 @@ int kivi_append_launch(const char* fn, KiviAppend& a, int D, int n, int group, i
     a.vslot = n % (a.R + 1);
     const int64_t nthr = (int64_t)a.B * (a.Hq + 2 * a.Hkv) * 64;
     const dim3 grid((unsigned)((nthr + 255) / 256));
-    if (bits == 2) hipLaunchKernelGGL(kivi_append_kernel<2>, grid, dim3(256), 0, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL(kivi_append_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, a);
+    if (a.inv_tab) {
+        if (bits == 2) hipLaunchKernelGGL((kivi_append_kernel<2, true>), grid, dim3(256), 0, (hipStream_t)stream, a);
+        else hipLaunchKernelGGL((kivi_append_kernel<4, true>), grid, dim3(256), 0, (hipStream_t)stream, a);
+    } else {
+        if (bits == 2) hipLaunchKernelGGL((kivi_append_kernel<2, false>), grid, dim3(256), 0, (hipStream_t)stream, a);
+        else hipLaunchKernelGGL((kivi_append_kernel<4, false>), grid, dim3(256), 0, (hipStream_t)stream, a);
+    }
     GEAR_CHECK_LAUNCH(fn);
     return 0;
 }
@@ -266,10 +272,9 @@ __global__ __launch_bounds__(256) void kivi_seam_kernel(KiviSeam v) {
 
 }  // namespace
 
-extern "C" int gear_kivi_rope_append(const void* qkv, int B, int Hq, int Hkv, int D, int pos, float theta, void* q_out, void* kwin,
-                                     int kslot, void* vring, int n, int R, int evict_row, void* vcode, void* vscale, void* vmn,
-                                     int tcap, int group, int bits, void* stream) {
-    GEAR_CHECK_ARG(Hq > 0 && theta > 0.0f, "gear_kivi_rope_append: Hq %d, theta %g", Hq, (double)theta);
+static int kivi_rope_append(const char* fn, const void* qkv, int B, int Hq, int Hkv, int D, int pos, float theta,
+                            const float* inv_freq, float attn_factor, void* q_out, void* kwin, int kslot, void* vring, int n, int R,
+                            int evict_row, void* vcode, void* vscale, void* vmn, int tcap, int group, int bits, void* stream) {
     KiviAppend a;
     const uint16_t* s = (const uint16_t*)qkv;
     a.qsrc = s;
@@ -277,11 +282,30 @@ extern "C" int gear_kivi_rope_append(const void* qkv, int B, int Hq, int Hkv, in
     a.vsrc = s ? s + (int64_t)(Hq + Hkv) * KD : nullptr;
     a.bstride = (int64_t)(Hq + 2 * Hkv) * KD;
     a.B = B; a.Hq = Hq; a.Hkv = Hkv; a.rope = 1; a.pos = pos;
-    a.log2_theta = log2f(theta);
+    a.log2_theta = inv_freq ? 0.0f : log2f(theta);
+    a.inv_tab = inv_freq; a.attn_factor = attn_factor;
     a.q_out = (uint16_t*)q_out; a.kwin = (uint16_t*)kwin; a.vring = (uint16_t*)vring;
     a.kslot = kslot; a.R = R; a.evict_row = evict_row;
     a.vcode = (uint32_t*)vcode; a.vscale = (uint16_t*)vscale; a.vmn = (uint16_t*)vmn; a.tcap = tcap;
-    return kivi_append_launch("gear_kivi_rope_append", a, D, n, group, bits, stream);
+    return kivi_append_launch(fn, a, D, n, group, bits, stream);
+}
+
+extern "C" int gear_kivi_rope_append(const void* qkv, int B, int Hq, int Hkv, int D, int pos, float theta, void* q_out, void* kwin,
+                                     int kslot, void* vring, int n, int R, int evict_row, void* vcode, void* vscale, void* vmn,
+                                     int tcap, int group, int bits, void* stream) {
+    GEAR_CHECK_ARG(Hq > 0 && theta > 0.0f, "gear_kivi_rope_append: Hq %d, theta %g", Hq, (double)theta);
+    return kivi_rope_append("gear_kivi_rope_append", qkv, B, Hq, Hkv, D, pos, theta, nullptr, 1.0f, q_out, kwin, kslot, vring, n, R,
+                            evict_row, vcode, vscale, vmn, tcap, group, bits, stream);
+}
+
+extern "C" int gear_kivi_rope_append_freq(const void* qkv, int B, int Hq, int Hkv, int D, int pos, const float* inv_freq,
+                                          float attn_factor, void* q_out, void* kwin, int kslot, void* vring, int n, int R,
+                                          int evict_row, void* vcode, void* vscale, void* vmn, int tcap, int group, int bits,
+                                          void* stream) {
+    GEAR_CHECK_ARG(Hq > 0, "gear_kivi_rope_append_freq: Hq %d", Hq);
+    GEAR_CHECK_ROPE_TABLE("gear_kivi_rope_append_freq", inv_freq, attn_factor);
+    return kivi_rope_append("gear_kivi_rope_append_freq", qkv, B, Hq, Hkv, D, pos, 0.0f, inv_freq, attn_factor, q_out, kwin, kslot,
+                            vring, n, R, evict_row, vcode, vscale, vmn, tcap, group, bits, stream);
 }
 
 extern "C" int gear_kivi_append(const void* k_new, const void* v_new, int B, int Hkv, int D, void* kwin, int kslot, void* vring,
@@ -292,6 +316,7 @@ extern "C" int gear_kivi_append(const void* k_new, const void* v_new, int B, int
     a.bstride = (int64_t)Hkv * KD;
     a.B = B; a.Hq = 0; a.Hkv = Hkv; a.rope = 0; a.pos = 0;
     a.log2_theta = 0.0f;
+    a.inv_tab = nullptr; a.attn_factor = 1.0f;
     a.q_out = nullptr; a.kwin = (uint16_t*)kwin; a.vring = (uint16_t*)vring;
     a.kslot = kslot; a.R = R; a.evict_row = evict_row;
     a.vcode = (uint32_t*)vcode; a.vscale = (uint16_t*)vscale; a.vmn = (uint16_t*)vmn; a.tcap = tcap;

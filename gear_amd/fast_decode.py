@@ -16,6 +16,7 @@ import torch.nn.functional as F
 from . import _lib as L
 from .cache import Fp16KVCache, GearKVCache, GearKVCachePool, KiviKVCache
 from .modeling_llamagear import apply_rotary_pos_emb
+from .rope import rope_parameters
 from .sampling import sample_tokens
 
 
@@ -60,6 +61,11 @@ class FastGearDecoder:
         self.theta = float(cfg.rope_theta)
         dev = model.lm_head.weight.device
         self.dev = dev
+        # rope_scaling (linear / llama3 / yarn): the token step reads the frequencies from a device table (the gear_*_freq entry
+        # points), the dense paths from the attention modules' ScaledRotaryEmbedding.  None: the theta code path, as before.
+        # (Every rank of a sharded decoder computes the same table from the same config; captured graphs keep its pointer.)
+        inv_freq, attn_factor = rope_parameters(cfg, self.D)
+        self.rope = None if inv_freq is None else (inv_freq.to(dev).contiguous(), float(attn_factor))
         self.layers = []
         cc0 = model.model.layers[0].self_attn.compress_config
         # pooled cache storage: block boundaries compress every layer's window in one launch sequence
@@ -215,21 +221,27 @@ class FastGearDecoder:
         if self.cache_kind == "kivi":
             # the projection (one fused launch for B <= 4), then gear_kivi_rope_append: RoPE, K window, V ring and the evicted
             # V row's codes in one launch
-            return cache.append_rope(self._norm_linear(res, lw["wqkv"]), self.Hq, self.pos, self.theta)
+            return cache.append_rope(self._norm_linear(res, lw["wqkv"]), self.Hq, self.pos, self.theta, rope=self.rope)
         if self._fused(B, K):
             if not dyn and cache.n_win >= cache.R:
                 raise L.GearError(f"FastGearDecoder: the cache window is full ({cache.n_win} of {cache.R} slots): capacity reached")
             q = torch.empty((B, self.Hq, 1, self.D), dtype=res.dtype, device=res.device)
-            rc = L.load().gear_gemv_qkv_rope(
-                L.ptr(res), None, None, self.eps, L.ptr(lw["wqkv"]), B, K, self.Hq, self.Hkv, self.D,
-                0 if dyn else self.pos, 0 if dyn else cache.n_win, cache.R, self.theta,
-                L.ptr(self.state) if dyn else None, None, L.ptr(q), L.ptr(cache.kwin), L.ptr(cache.vwin), L.stream_ptr())
-            L.check(rc, "gear_gemv_qkv_rope")
+            head = (L.ptr(res), None, None, self.eps, L.ptr(lw["wqkv"]), B, K, self.Hq, self.Hkv, self.D,
+                    0 if dyn else self.pos, 0 if dyn else cache.n_win, cache.R)
+            tail = (L.ptr(self.state) if dyn else None, None, L.ptr(q), L.ptr(cache.kwin), L.ptr(cache.vwin), L.stream_ptr())
+            if self.rope is None:
+                rc = L.load().gear_gemv_qkv_rope(*head, self.theta, *tail)
+                L.check(rc, "gear_gemv_qkv_rope")
+            else:
+                rc = L.load().gear_gemv_qkv_rope_freq(*head, L.ptr(self.rope[0]), self.rope[1], *tail)
+                L.check(rc, "gear_gemv_qkv_rope_freq")
             if not dyn:
                 cache.n_win += 1
             return q
         qkv = F.linear(self._unit_rms(res), lw["wqkv"])
-        return cache.append_rope_dyn(qkv, self.Hq, self.theta) if dyn else cache.append_rope(qkv, self.Hq, self.pos, self.theta)
+        if dyn:
+            return cache.append_rope_dyn(qkv, self.Hq, self.theta, rope=self.rope)
+        return cache.append_rope(qkv, self.Hq, self.pos, self.theta, rope=self.rope)
 
     # ------------------------------------------------------------------------------------------------ prefill
     @torch.no_grad()

@@ -34,6 +34,7 @@ from torch import nn
 
 from . import _lib as L
 from .quant.matmul import cuda_bmm_fA_qB_outer
+from .rope import ScaledRotaryEmbedding, device_table, rotary_embedding
 from .sampling import SamplingParams, sample_tokens
 from .quant.new_pack import (headwise_lrap, triton_quantize_and_pack_along_last_dim,
                              triton_quantize_and_pack_along_last_dim_witherror)
@@ -359,7 +360,9 @@ class LlamaAttention_GEAR(nn.Module):
         self.k_proj = nn.Linear(self.hidden_size, self.num_key_value_heads * self.head_dim, bias=bias)
         self.v_proj = nn.Linear(self.hidden_size, self.num_key_value_heads * self.head_dim, bias=bias)
         self.o_proj = nn.Linear(self.total_heads * self.head_dim, self.hidden_size, bias=bias)
-        self.rotary_emb = LlamaRotaryEmbedding(self.head_dim, self.max_position_embeddings, self.rope_theta)
+        # config.rope_scaling (linear / llama3 / yarn): the scaled table's module; none / "default": the stock one
+        self.rotary_emb = rotary_embedding(config, self.head_dim, lambda: LlamaRotaryEmbedding(
+            self.head_dim, self.max_position_embeddings, self.rope_theta))
 
     # ---- cache transitions -----------------------------------------------------------------------------------
     def _prefill_cache(self, key_states, value_states):
@@ -475,6 +478,20 @@ class LlamaAttention_GEAR(nn.Module):
             self._wqkv_folded_key = key
         return self._wqkv_folded
 
+    def _rope_table(self, dev):
+        """(inv_freq device table, attn_factor) of a scaled rotary module for the gear_*_freq entry points; None: theta."""
+        return device_table(self.rotary_emb, dev)
+
+    def _gemv_qkv_rope(self, head, tail, dev):
+        """gear_gemv_qkv_rope(head..., theta, tail...), or its table flavour for a scaled model."""
+        rope = self._rope_table(dev)
+        if rope is None:
+            rc = L.load().gear_gemv_qkv_rope(*head, float(self.rope_theta), *tail)
+            L.check(rc, "gear_gemv_qkv_rope")
+        else:
+            rc = L.load().gear_gemv_qkv_rope_freq(*head, L.ptr(rope[0]), rope[1], *tail)
+            L.check(rc, "gear_gemv_qkv_rope_freq")
+
     def decode_token_fused(self, res, delta, norm_weight, eps: float, hc: GearHookCache, dyn=None, fold: bool = False):
         """The hook's decode step for the decoder layer's fused path (batch <= 4, implicit positions, stock rotary, no bias, one
         rank): [residual add + RMSNorm + q/k/v GEMV + RoPE + window append] = ONE launch (gear_gemv_qkv_rope), fused attention over
@@ -490,11 +507,10 @@ class LlamaAttention_GEAR(nn.Module):
             # {pos, slot, T, W}; no host-side counter moves here
             res1 = torch.empty_like(res) if delta is not None else res
             q = torch.empty((B, self.num_heads, 1, self.head_dim), dtype=res.dtype, device=res.device)
-            rc = L.load().gear_gemv_qkv_rope(L.ptr(res), L.ptr(delta), L.ptr(norm_weight), eps, L.ptr(wqkv), B, K,
-                                             self.num_heads, self.num_key_value_heads, self.head_dim, 0, 0, c.R,
-                                             float(self.rope_theta), L.ptr(dyn), L.ptr(res1) if delta is not None else None, L.ptr(q),
-                                             L.ptr(c.kwin), L.ptr(c.vwin), L.stream_ptr(res))
-            L.check(rc, "gear_gemv_qkv_rope")
+            self._gemv_qkv_rope((L.ptr(res), L.ptr(delta), L.ptr(norm_weight), eps, L.ptr(wqkv), B, K, self.num_heads,
+                                 self.num_key_value_heads, self.head_dim, 0, 0, c.R),
+                                (L.ptr(dyn), L.ptr(res1) if delta is not None else None, L.ptr(q), L.ptr(c.kwin), L.ptr(c.vwin),
+                                 L.stream_ptr(res)), res.device)
             return res1, c.attend_dyn(q).view(B, self.num_heads * self.head_dim), None
         hc.check_live()
         if c.n_comp + c.n_win + 1 > c.Tmax:
@@ -503,11 +519,10 @@ class LlamaAttention_GEAR(nn.Module):
         kv_seq_len = hc.seq_len + 1
         res1 = torch.empty_like(res) if delta is not None else res
         q = torch.empty((B, self.num_heads, 1, self.head_dim), dtype=res.dtype, device=res.device)
-        rc = L.load().gear_gemv_qkv_rope(L.ptr(res), L.ptr(delta), L.ptr(norm_weight), eps, L.ptr(wqkv), B, K,
-                                         self.num_heads, self.num_key_value_heads, self.head_dim, kv_seq_len - 1, c.n_win, c.R,
-                                         float(self.rope_theta), None, L.ptr(res1) if delta is not None else None, L.ptr(q),
-                                         L.ptr(c.kwin), L.ptr(c.vwin), L.stream_ptr(res))
-        L.check(rc, "gear_gemv_qkv_rope")
+        self._gemv_qkv_rope((L.ptr(res), L.ptr(delta), L.ptr(norm_weight), eps, L.ptr(wqkv), B, K, self.num_heads,
+                             self.num_key_value_heads, self.head_dim, kv_seq_len - 1, c.n_win, c.R),
+                            (None, L.ptr(res1) if delta is not None else None, L.ptr(q), L.ptr(c.kwin), L.ptr(c.vwin),
+                             L.stream_ptr(res)), res.device)
         c.n_win += 1
         out = c.attend(q)
         if c.n_win == c.R:
@@ -526,7 +541,8 @@ class LlamaAttention_GEAR(nn.Module):
         if qkv_flat is not None:
             # RoPE at position kv_seq_len - 1 on q and k + window append in ONE launch (gear_rope_append: the reference's
             # rotary arithmetic op by op, :203-205) instead of ~25 eager ops
-            query_states = c.append_rope(qkv_flat, self.num_heads, kv_seq_len - 1, float(self.rope_theta))
+            query_states = c.append_rope(qkv_flat, self.num_heads, kv_seq_len - 1, float(self.rope_theta),
+                                         rope=self._rope_table(qkv_flat.device))
         else:
             c.append(key_states, value_states)
         out = c.attend(query_states)
@@ -553,7 +569,8 @@ class LlamaAttention_GEAR(nn.Module):
                    and (attention_mask is None or self.decode_mask_is_zero))
         # implicit positions (the model passes none at decode: the token sits at kv_seq_len - 1) and the stock rotary module:
         # RoPE is fused with the window append below; anything else takes the reference's rotary code
-        fused_rope = (fast_ok and self.fused_rope and position_ids is None and type(self.rotary_emb) is LlamaRotaryEmbedding
+        fused_rope = (fast_ok and self.fused_rope and position_ids is None
+                      and type(self.rotary_emb) in (LlamaRotaryEmbedding, ScaledRotaryEmbedding)
                       and hidden_states.dtype == torch.float16)
         if not fused_rope:
             if position_ids is None:
@@ -730,7 +747,7 @@ class LlamaDecoderLayer_GEAR(nn.Module):
         """The layer's token step can run as the six fused launches (batch <= 4, pre-allocated cache, one rank, stock rotary, no biases)."""
         at, mlp = self.self_attn, self.mlp
         return (B <= 4 and isinstance(past, GearHookCache) and at.tp_world == 1 and at.q_proj.bias is None and at.fused_rope
-                and at.fast_decode and type(at.rotary_emb) is LlamaRotaryEmbedding and mlp.down_proj.bias is None
+                and at.fast_decode and type(at.rotary_emb) in (LlamaRotaryEmbedding, ScaledRotaryEmbedding) and mlp.down_proj.bias is None
                 and mlp.gate_proj.weight.shape[0] % 2 == 0)
 
     def decode_step(self, res: torch.Tensor, delta: Optional[torch.Tensor], past, dyn=None):

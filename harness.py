@@ -71,7 +71,8 @@ def build(variant, mcfg, cc, dev):
 def run(variant, args, dev):
     from gear_amd.modeling_llamagear import LlamaConfigLite
     mcfg = LlamaConfigLite(num_hidden_layers=args.layers, max_position_embeddings=max(4096, args.max_length + 64),
-                           k_bits=args.bits, v_bits=args.bits, group_size=args.group_size, residual_length=args.residual)
+                           k_bits=args.bits, v_bits=args.bits, group_size=args.group_size, residual_length=args.residual,
+                           rope_scaling=args.rope_scaling)
     cc = dict(compress_method=args.compress_method, group_size=args.group_size, residual=args.residual, quantize_bit=args.bits,
               rank=args.rank, rankv=args.rank, loop=args.loop, left=args.left)
     model = build(variant, mcfg, cc, dev)
@@ -142,6 +143,7 @@ def run(variant, args, dev):
     torch.cuda.empty_cache()
     return dict(variant=variant, fast=bool(args.fast), batch_size=args.batch_size, prompt_len=args.prompt_len,
                 max_length=int(out.shape[1]), time_s=dt, new_tokens_per_s=new / dt, peak_mem_MiB=peak, layers=args.layers,
+                rope_scaling=args.rope_scaling,
                 **(dict(cache_bytes=cache_bytes) if cache_bytes is not None else {}),
                 **(dict(shared_prefix=True) if args.shared_prefix and variant == "gearl" else {}),
                 **(dict(num_beams=beams, length_penalty=args.length_penalty, best_score=float(beam_scores[0])) if beams else {}),
@@ -173,6 +175,9 @@ def main():
     ap.add_argument("--tree_width", type=int, default=0,
                     help="with --fast: generate_speculative with n-gram drafts (n_draft 7); 1: draft chains, N > 1: draft trees of "
                          "up to N continuations per pass (greedy only)")
+    ap.add_argument("--rope_scaling", type=json.loads, default=None,
+                    help="the config's rope_scaling as JSON, e.g. '{\"rope_type\": \"llama3\", \"factor\": 8, \"low_freq_factor\": 1, "
+                         "\"high_freq_factor\": 4, \"original_max_position_embeddings\": 8192}' (linear / llama3 / yarn; default: none)")
     ap.add_argument("--json", action="store_true")
     # sampling, with the defaults of GenerationBench/GenerationTest/evaluation_bbh_cot.py:381-390
     ap.add_argument("--do_sample", action="store_true", help="sample (temperature / top-k / top-p) instead of greedy decoding")

@@ -656,6 +656,25 @@ size_t gear_attn_decode_kivi_workspace(int B, int Hq, int T, int bits);
 int gear_attn_decode_kivi(const gear_cache_view* c, const void* q, int Hq, int L, int Tk, int Nv, float qscale, void* out, void* lse,
                           void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- RoPE scaling (config.rope_scaling: linear / llama3 / yarn): the frequency-table flavours of the RoPE entry points -------
+ * Each takes its parent's arguments with `float theta` replaced by `const float* inv_freq` -- a DEVICE pointer to the 64 fp32
+ * inverse frequencies of the rotation pairs (gear_amd/rope.py: rope_parameters) -- and `float attn_factor` (yarn's cos / sin
+ * scale; 1 otherwise):  ang = (float)pos * inv_freq[p], cos = fp16(cosf(ang) * attn_factor), sin alike, then the parent's fp16
+ * op-by-op rotation.  Everything else -- V copy, window / ring writes, the KIVI eviction, the device state of the dyn flavours --
+ * is the parent's code (one kernel template, `bool TAB`).  A null table and an attn_factor that is not positive and finite are
+ * refused before any launch, as is whatever the parent refuses.  The table is read at run time: a captured graph keeps the
+ * pointer, so the buffer must outlive it. */
+int gear_rope_append_freq(const void* qkv, int B, int Hq, int Hkv, int D, int pos, const float* inv_freq, float attn_factor,
+                          void* q_out, void* kwin, void* vwin, int slot, int W, void* stream);
+int gear_rope_append_dyn_freq(const void* qkv, int B, int Hq, int Hkv, int D, const void* dyn_state, const float* inv_freq,
+                              float attn_factor, void* q_out, void* kwin, void* vwin, int W, void* stream);
+int gear_gemv_qkv_rope_freq(const void* x, const void* delta, const void* norm_w, float eps, const void* Wqkv, int B, int K,
+                            int Hq, int Hkv, int D, int pos, int slot, int wcap, const float* inv_freq, float attn_factor,
+                            const void* dyn_state, void* res_out, void* q_out, void* kwin, void* vwin, void* stream);
+int gear_kivi_rope_append_freq(const void* qkv, int B, int Hq, int Hkv, int D, int pos, const float* inv_freq, float attn_factor,
+                               void* q_out, void* kwin, int kslot, void* vring, int n, int R, int evict_row, void* vcode,
+                               void* vscale, void* vmn, int tcap, int group, int bits, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
