@@ -344,6 +344,18 @@ __global__ __launch_bounds__(TB, (TB == 256 ? 2 : 1)) void decompress_rows_kerne
             op[1] = d1;
         }
     };
+    // two fp32 results of the dot-product chain or of the matrix cores -> packed fp16, as the compiler's own v_cvt_pk_f16_f32 and not
+    // common.h's inline-asm f2h2_bits: neither unit's results are interlocked on gfx950 (a VALU read of a register that a
+    // v_dot2 has just written needs 3 wait states, one that a v_mfma has written more), the wait states are the compiler's to
+    // insert, and it cannot see into an asm statement.  With 1024 threads (rank 16: the 128 registers make the compiler finish one
+    // pair of columns at a time) the asm conversion sat directly behind the last v_dot2c of its own operand and now and then read
+    // the accumulator from before that instruction: one element of a row off by its last two products, differently from run to run
+    // (found by tests/test_gpu_decompress.py, V rows of 16384 columns at rank 16).
+    typedef float float2c __attribute__((ext_vector_type(2)));
+    auto cvt2 = [](float a, float b) __attribute__((always_inline)) {
+        const float2c v = {a, b};
+        return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, half2_t));
+    };
     // (swp: exchange the store halves between lanes l and l + 32 -- every lane of the wave must be in this call)
     auto compute_row = [&](int ri, const RowIn& cur, const bool table, const bool swp) __attribute__((always_inline)) {
         float f[16];
@@ -363,8 +375,8 @@ __global__ __launch_bounds__(TB, (TB == 256 ? 2 : 1)) void decompress_rows_kerne
                     f[j] = acc;
                 }
                 // (v_cvt_pk_f16_f32: two results per conversion, round-to-nearest-even like the single one)
-                d0 = make_uint4(f2h2_bits(f[0], f[1]), f2h2_bits(f[2], f[3]), f2h2_bits(f[4], f[5]), f2h2_bits(f[6], f[7]));
-                d1 = make_uint4(f2h2_bits(f[8], f[9]), f2h2_bits(f[10], f[11]), f2h2_bits(f[12], f[13]), f2h2_bits(f[14], f[15]));
+                d0 = make_uint4(cvt2(f[0], f[1]), cvt2(f[2], f[3]), cvt2(f[4], f[5]), cvt2(f[6], f[7]));
+                d1 = make_uint4(cvt2(f[8], f[9]), cvt2(f[10], f[11]), cvt2(f[12], f[13]), cvt2(f[14], f[15]));
             } else {
                 unpack8(d0, f);
                 unpack8(d1, f + 8);
@@ -429,15 +441,8 @@ __global__ __launch_bounds__(TB, (TB == 256 ? 2 : 1)) void decompress_rows_kerne
                         if (RV == 4) { const uint2 t = *(const uint2*)fvp; in.fva = make_uint4(t.x, t.y, 0, 0); }
                         else in.fva = *(const uint4*)fvp;
                     };
-                    // (the conversion as the compiler's own v_cvt_pk_f16_f32, not common.h's inline-asm f2h2_bits: the matrix cores'
-                    // results are not interlocked, the wait states in front of their first reader are the compiler's to insert, and it
-                    // cannot see into an asm statement -- with f2h2_bits the first row of every group read accumulators that the
-                    // later columns' instructions had not written yet)
-                    typedef float float2c __attribute__((ext_vector_type(2)));
-                    auto cvt2 = [](float a, float b) __attribute__((always_inline)) {
-                        const float2c v = {a, b};
-                        return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, half2_t));
-                    };
+                    // (the conversion is cvt2, not f2h2_bits: see there -- with f2h2_bits the first row of every group read
+                    // accumulators that the later columns' instructions had not written yet)
                     auto compute4 = [&](int gi, const RowIn4& in) __attribute__((always_inline)) {
                         const int p0 = phys(4 * gi);
                         float4_t acc[16];
