@@ -110,6 +110,8 @@ SIGNATURES = {
                                      _vp, _vp, _vp, _vp, _vp]),
     "gear_kivi_rope_append_freq": (_i, [_vp, _i, _i, _i, _i, _i, _vp, C.c_float, _vp, _vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _i,
                                         _i, _i, _vp]),
+    # scoring (csrc/logprob.hip): logits, ref_logits, ids, N, V, ld, k_top, lp, lse, rank, kl, agree, top_idx, top_lp, stream
+    "gear_token_logprobs": (_i, [_vp, _vp, _vp, _i64, _i, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
 ABI_VERSION = 5      # what this table was written against (gear_abi_version() of the library must match)

@@ -950,7 +950,8 @@ class FastGearDecoder:
 
     @torch.no_grad()
     def generate(self, input_ids: torch.Tensor, max_length: int, graph: bool = False, sampling=None,
-                 shared_prefix: bool = False, suffix_ids: torch.Tensor = None, reuse_prefix: bool = False) -> torch.Tensor:
+                 shared_prefix: bool = False, suffix_ids: torch.Tensor = None, reuse_prefix: bool = False,
+                 return_logprobs: bool = False):
         """Greedy decoding; with `sampling` (a sampling.SamplingParams) every token is drawn by gear_sample_tokens at its own
         position -- the first from the prefill logits, the rest from step()'s (graph=True: step_graph_sampled(), same tokens).
         shared_prefix=True (a decoder built with shared_prefix_tokens > 0): input_ids is ONE prompt [1, T], the result is
@@ -960,31 +961,64 @@ class FastGearDecoder:
         then extend_shared(suffix_ids); the first token comes from the last extend row (sampler position T + n).  Rows of the
         result are prompt | suffix_s | generated, and max_length counts all of it.
         reuse_prefix=True (with shared_prefix): when a prompt is already stored, skip the prefill and reset_shared() instead --
-        input_ids must be the stored prompt (ValueError otherwise)."""
+        input_ids must be the stored prompt (ValueError otherwise).
+        return_logprobs=True: returns (tokens, logprobs) -- logprobs fp32 [B, generated tokens], the log-softmax of each step's raw
+        logits at the emitted token (before temperature / top-k / top-p: HF's compute_transition_scores on unprocessed scores),
+        one gear_token_logprobs launch per step on the step's fp16 logits (graph=True: eagerly after each replay, on the graph's
+        static logits buffer; the captured graphs are unchanged).  The tokens are those of the same call without it."""
         if shared_prefix and graph:
             raise NotImplementedError("generate(shared_prefix=True, graph=True): shared-prefix decoding has eager steps only")
         if graph or shared_prefix:
             self._kivi_refused("generate(graph=True)" if graph else "generate(shared_prefix=True)")
         if (suffix_ids is not None or reuse_prefix) and not shared_prefix:
             raise ValueError("generate(): suffix_ids / reuse_prefix need shared_prefix=True")
+        lps = [] if return_logprobs else None      # one [B] column of log-probs per emitted token
         if sampling is not None:
-            return self._generate_sampled(input_ids, max_length, graph, sampling, shared_prefix, suffix_ids, reuse_prefix)
+            toks = self._generate_sampled(input_ids, max_length, graph, sampling, shared_prefix, suffix_ids, reuse_prefix, lps)
+            return (toks, torch.stack(lps, 1)) if return_logprobs else toks
         logits, out = self._generate_start(input_ids, max_length, shared_prefix, suffix_ids, reuse_prefix)
         nxt = logits.argmax(-1, keepdim=True)
+        self._record_logprobs(lps, logits, nxt)
         out.append(nxt)
         if graph and sum(t.shape[1] for t in out) < max_length:
-            nxt = self.step(nxt).argmax(-1, keepdim=True)      # one eager step warms up every library handle
+            logits = self.step(nxt)                            # one eager step warms up every library handle
+            nxt = logits.argmax(-1, keepdim=True)
+            self._record_logprobs(lps, logits, nxt)
             out.append(nxt)
             self.tok.copy_(nxt)
         while sum(t.shape[1] for t in out) < max_length:
             if graph:
                 nxt = self.step_graph().clone()
+                self._record_logprobs(lps, self.logits_static, nxt)
             else:
-                nxt = self.step(nxt).argmax(-1, keepdim=True)
+                logits = self.step(nxt)
+                nxt = logits.argmax(-1, keepdim=True)
+                self._record_logprobs(lps, logits, nxt)
             out.append(nxt)
         self.check_exchange()
         self.check_block_kernel()
-        return torch.cat(out, dim=1)
+        toks = torch.cat(out, dim=1)
+        return (toks, torch.stack(lps, 1)) if return_logprobs else toks
+
+    @staticmethod
+    def _record_logprobs(lps, logits, tok):
+        """generate(return_logprobs=True): the log-prob of the emitted tokens tok [B, 1] under the step's raw logits [B, V]."""
+        if lps is not None:
+            from .scoring import token_logprobs
+            lps.append(token_logprobs(logits, tok.reshape(-1)).logprobs)
+
+    def score(self, input_ids: torch.Tensor, prompt_len: int, mode: str = "step", chunk: int = 512, top_k: int = 0):
+        """Teacher-forced scoring of input_ids [B, T] on an empty decoder: prefill(input_ids[:, :prompt_len]), then the remaining
+        tokens are fed and position t's log-prob is read from the logits that predict token t.  Returns a scoring.ScoreResult over
+        the positions prompt_len .. T - 1 (logprobs, rank, nll, perplexity, top1; top_k > 0: the top log-probs of every position).
+        mode="step": one step() per token -- every prediction sees exactly the cache a decoder would see at that point (the faithful
+        measure of decode-time quality); every cache kind.  mode="extend": pieces of `chunk` tokens through extend() -- fast, but
+        the tokens inside a piece see each other uncompressed; "gear" and "fp16" only (KIVI: extend()'s NotImplementedError).
+        The decoder is left as the same prefill + step / extend calls leave it (the last token is a target only: T - 1 tokens
+        are fed); a text that cannot fit is refused before anything changes.  The logits are read in place by gear_token_logprobs,
+        one piece ([B, chunk, V] fp16) at a time: no fp32 copy, nothing wider than a piece."""
+        from .scoring import score
+        return score(self, input_ids, prompt_len, mode, chunk, top_k)
 
     def _generate_start(self, input_ids, max_length, shared_prefix, suffix_ids, reuse_prefix):
         """The prompt phase of generate(): (logits [B, vocab] the first token is taken from, the token columns so far)."""
@@ -1007,19 +1041,26 @@ class FastGearDecoder:
             out.append(suffix_ids)
         return logits, out
 
-    def _generate_sampled(self, input_ids, max_length, graph, sampling, shared_prefix=False, suffix_ids=None, reuse_prefix=False):
+    def _generate_sampled(self, input_ids, max_length, graph, sampling, shared_prefix=False, suffix_ids=None, reuse_prefix=False,
+                          lps=None):
         logits, out = self._generate_start(input_ids, max_length, shared_prefix, suffix_ids, reuse_prefix)
         nxt = self._sample(logits, sampling)
+        self._record_logprobs(lps, logits, nxt)
         out.append(nxt)
         if graph and sum(t.shape[1] for t in out) < max_length:
-            nxt = self._sample(self.step(nxt), sampling)        # one eager step warms up every library handle
+            logits = self.step(nxt)                             # one eager step warms up every library handle
+            nxt = self._sample(logits, sampling)
+            self._record_logprobs(lps, logits, nxt)
             out.append(nxt)
             self.tok.copy_(nxt)
         while sum(t.shape[1] for t in out) < max_length:
             if graph:
                 nxt = self.step_graph_sampled(sampling).clone()
+                self._record_logprobs(lps, self.logits_sampled_static, nxt)
             else:
-                nxt = self._sample(self.step(nxt), sampling)
+                logits = self.step(nxt)
+                nxt = self._sample(logits, sampling)
+                self._record_logprobs(lps, logits, nxt)
             out.append(nxt)
         self.check_exchange()
         self.check_block_kernel()

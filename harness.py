@@ -151,6 +151,34 @@ def run(variant, args, dev):
                    if args.do_sample else {}))
 
 
+def score(args, dev):
+    """--score --fast: the harness's synthetic text (prompt_len prompt tokens, scored up to max_length) teacher-forced through the
+    three cache kinds of FastGearDecoder in lockstep, one step() per token (scoring.compare_caches): mean NLL, perplexity and
+    top-1 share per kind, mean KL and argmax agreement of the compressed kinds against the fp16 row."""
+    from gear_amd.modeling_llamagear import LlamaConfigLite
+    from gear_amd.scoring import compare_caches
+    mcfg = LlamaConfigLite(num_hidden_layers=args.layers, max_position_embeddings=max(4096, args.max_length + 64),
+                           k_bits=args.bits, v_bits=args.bits, group_size=args.group_size, residual_length=args.residual,
+                           rope_scaling=args.rope_scaling)
+    cc = dict(compress_method=args.compress_method, group_size=args.group_size, residual=args.residual, quantize_bit=args.bits,
+              rank=args.rank, rankv=args.rank, loop=args.loop, left=args.left)
+    model = build("gearl", mcfg, cc, dev)
+    torch.manual_seed(1)
+    ids = torch.randint(0, mcfg.vocab_size, (args.batch_size, args.max_length), device=dev)
+    kinds = ("fp16", "gear", "kivi")
+    res = compare_caches(model, ids, args.prompt_len, kinds=kinds, max_tokens=args.max_length + 8)
+    print(f"scoring {args.max_length - args.prompt_len} positions x batch {args.batch_size} after a {args.prompt_len}-token prompt "
+          f"({args.layers} layers, mode step)")
+    print(f"{'cache':6s} {'mean NLL':>10s} {'perplexity':>12s} {'top-1':>7s} {'mean KL vs fp16':>16s} {'argmax agree':>13s}")
+    out = []
+    for kind, r in zip(kinds, res):
+        kl = "" if r.kl_mean is None else f"{r.kl_mean:.6f}"
+        ag = "" if r.agree_rate is None else f"{r.agree_rate:.4f}"
+        print(f"{kind:6s} {r.nll:10.5f} {r.perplexity:12.3f} {r.top1:7.4f} {kl:>16s} {ag:>13s}")
+        out.append(dict(cache_kind=kind, nll=r.nll, perplexity=r.perplexity, top1=r.top1, kl_mean=r.kl_mean, agree=r.agree_rate))
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description="GEAR / KIVI / fp16 generation timing (cuda_supported_gear/test.py)")
     ap.add_argument("--batch_size", type=int, default=8, help="Batch size.")                       # test.py:22
@@ -179,6 +207,9 @@ def main():
                     help="the config's rope_scaling as JSON, e.g. '{\"rope_type\": \"llama3\", \"factor\": 8, \"low_freq_factor\": 1, "
                          "\"high_freq_factor\": 4, \"original_max_position_embeddings\": 8192}' (linear / llama3 / yarn; default: none)")
     ap.add_argument("--json", action="store_true")
+    ap.add_argument("--score", action="store_true",
+                    help="with --fast: score the synthetic text through the fp16 / gear / kivi caches (mean NLL, perplexity, top-1; "
+                         "KL and argmax agreement against the fp16 row) instead of timing a generation")
     # sampling, with the defaults of GenerationBench/GenerationTest/evaluation_bbh_cot.py:381-390
     ap.add_argument("--do_sample", action="store_true", help="sample (temperature / top-k / top-p) instead of greedy decoding")
     ap.add_argument("--temperature", type=float, default=0.8)
@@ -198,8 +229,15 @@ def main():
         raise SystemExit("--tree_width needs --fast without --shared_prefix (speculative decoding lives in FastGearDecoder)")
     if args.tree_width > 1 and args.do_sample:
         raise SystemExit("--tree_width > 1 and --do_sample exclude each other (sampling over a draft tree is not implemented)")
+    if args.score and not args.fast:
+        raise SystemExit("--score needs --fast (scoring lives in FastGearDecoder)")
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
+    if args.score:
+        res = score(args, dev)
+        if args.json:
+            print(json.dumps(res))
+        return
     variants = ["gearl", "KIVI", "None"] if args.all else [v for v in ("gearl", "KIVI", "None") if v in args.model]
     if not variants:
         raise SystemExit('--model must contain "gearl", "KIVI" or "None"')

@@ -675,6 +675,38 @@ int gear_kivi_rope_append_freq(const void* qkv, int B, int Hq, int Hkv, int D, i
                                void* q_out, void* kwin, int kslot, void* vring, int n, int R, int evict_row, void* vcode,
                                void* vscale, void* vmn, int tcap, int group, int bits, void* stream);
 
+/* ---- scoring: per-token log-probs, rank, KL against a second set of logits and the top-k log-probs, one launch ----------------
+ * logits fp16 [N, V] with a row pitch ld >= V (elements); ids int64 [N] = the target token of each row; ref_logits (optional):
+ * a second fp16 matrix of the same shape and pitch, the other cache's logits for the same tokens; k_top in [0, 8].
+ * Outputs (each may be NULL, except lp):
+ *   lp      fp32  [N]        logits[i, ids[i]] - logsumexp(logits[i, :])
+ *   lse     fp32  [N]        the log-sum-exp
+ *   rank    int32 [N]        entries strictly greater than the target's logit (0 = the target is the argmax)
+ *   kl      fp32  [N]        KL(softmax(ref_logits[i]) || softmax(logits[i])) in nats            (needs ref_logits)
+ *   agree   int32 [N]        1 where both rows have the same argmax (equal values: lowest index) (needs ref_logits)
+ *   top_idx int32 [N, k_top], top_lp fp32 [N, k_top]   the k_top largest log-probs, descending; equal values by index, lowest first
+ * Semantics:
+ *   - one workgroup per row (rows ride on gridDim.x: N may exceed 65535); a row is never split over workgroups, the workgroup
+ *     size is a function of V alone and every merge runs in a fixed order: a row's results depend on that row's contents only,
+ *     not on N or on the row's position, and the same call on the same data gives the same bits;
+ *   - one streaming pass with a running maximum: the statistics are fp32 sums of exp(x - max), so logits up to fp16's largest
+ *     value cannot overflow; the final log / subtraction run in fp64 and are rounded once.  k_top > 1 re-reads the row
+ *     k_top - 1 times (cache-resident: the workgroup has just read it);
+ *   - -inf logits (a masked vocabulary entry) contribute 0 to the sum; a target whose logit is -inf gives lp = -inf; a row that
+ *     is all -inf gives NaN in lp, lse (and kl, top_lp);
+ *   - ids[i] < 0 marks an ignored row (HF's -100): lp = 0, rank = -1; ids[i] >= V gives lp = NaN, rank = -1; neither indexes a read;
+ *   - kl = sum_j p_j (ref_j - x_j) - lse(ref) + lse(x): an entry with ref_j = -inf contributes 0, an entry with x_j = -inf under a
+ *     finite ref_j makes it +inf;
+ *   - loads are 16 bytes wide when a row (and its ref_logits row) starts on a 16-byte boundary; a row that does not (an odd ld, a
+ *     sliced view) is read with the widest loads its 2-byte alignment allows -- the same columns in the same order, so the bits do
+ *     not depend on where a row lies.  The V % 8 columns behind the last whole vector are read one by one.  Nothing past column
+ *     V - 1 of a row is read;
+ * Refused with a status < 0 and a gear_last_error message before any launch: null logits / ids / lp, V <= 0, N < 0 (or > 2^31 - 1),
+ * ld < V, k_top outside [0, 8] or > V, kl or agree without ref_logits.  N == 0 returns 0 without a launch. */
+int gear_token_logprobs(const void* logits, const void* ref_logits, const int64_t* ids, int64_t N, int V, int64_t ld, int k_top,
+                        float* lp, float* lse, int32_t* rank, float* kl, int32_t* agree, int32_t* top_idx, float* top_lp,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif
