@@ -112,6 +112,10 @@ SIGNATURES = {
                                         _i, _i, _vp]),
     # scoring (csrc/logprob.hip): logits, ref_logits, ids, N, V, ld, k_top, lp, lse, rank, kl, agree, top_idx, top_lp, stream
     "gear_token_logprobs": (_i, [_vp, _vp, _vp, _i64, _i, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    # logits processors (csrc/logits.hip): logits, out, fp32, B, V, ld, ld_out, hist, hist_cap, pos_dev, pos0, cur, prompt_len, params, stream
+    "gear_logits_process": (_i, [_vp, _vp, _i, _i, _i, _i64, _i64, _vp, _i, _vp, _i, _vp, _i, _vp, _vp]),
+    # tok, done, B, eos (host int[n_eos]), n_eos, pad, n_done, stream
+    "gear_eos_update": (_i, [_vp, _vp, _i, _vp, _i, _i64, _vp, _vp]),
 }
 
 ABI_VERSION = 5      # what this table was written against (gear_abi_version() of the library must match)
@@ -204,6 +208,12 @@ class CacheView(C.Structure):
 class SampleParamsC(C.Structure):
     """ctypes mirror of `gear_sample_params` (include/gear_hip.h)."""
     _fields_ = [("temperature", C.c_float), ("top_k", C.c_int), ("top_p", C.c_float), ("reserved", C.c_int), ("seed", C.c_uint64)]
+
+
+class LogitsParamsC(C.Structure):
+    """ctypes mirror of `gear_logits_params` (include/gear_hip.h)."""
+    _fields_ = [("repetition_penalty", C.c_float), ("no_repeat_ngram", C.c_int), ("min_new_tokens", C.c_int), ("n_eos", C.c_int),
+                ("eos", C.c_int * 8), ("n_bias", C.c_int), ("reserved", C.c_int), ("bias", C.c_void_p)]
 
 
 def stream_ptr(t=None) -> int:

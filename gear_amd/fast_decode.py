@@ -17,7 +17,8 @@ from . import _lib as L
 from .cache import Fp16KVCache, GearKVCache, GearKVCachePool, KiviKVCache
 from .modeling_llamagear import apply_rotary_pos_emb
 from .rope import rope_parameters
-from .sampling import sample_tokens
+from .logits import LogitsParams, TokenHistory, eos_ids, eos_update, process_logits
+from .sampling import SamplingParams, sample_tokens
 
 
 class FastGearDecoder:
@@ -135,6 +136,10 @@ class FastGearDecoder:
         self.graph_sampled = None     # the sampled token step (step_graph_sampled) and the params it was captured with
         self._graph_sampling = None
         self.logits_sampled_static = None
+        self.graph_proc = None        # the token step with logits processors / EOS bookkeeping (_generate_processed) and its key
+        self._graph_proc_key = None
+        self.logits_proc_static = None
+        self._proc_state = None       # history, processed-logits buffer, done flags: the buffers that graph points at
         self._state_dirty = True      # host counters moved without the device-side state (eager step / prefill)
         self.tok = torch.zeros((batch, 1), dtype=torch.long, device=dev)
         self.logits_static = None
@@ -301,6 +306,12 @@ class FastGearDecoder:
             raise NotImplementedError(f"{what}: not implemented for the KIVI cache (cache_kind='kivi'): it has prefill(), eager "
                                       "step() and generate() only")
 
+    @staticmethod
+    def _logits_refused(what, logits):
+        if logits is not None:
+            raise NotImplementedError(f"{what}: logits processors (logits=LogitsParams) are not implemented here: they run in "
+                                      "generate() only (eager steps on every cache kind, graph steps on the compressed cache)")
+
     def _shared_refused(self, what, hint=""):
         if self.shared_live:
             raise NotImplementedError(f"{what}: not implemented while a shared prefix is live (shared-prefix decoding has eager "
@@ -443,11 +454,12 @@ class FastGearDecoder:
         return (c0.Tmax - c0.n_comp) // c0.R * c0.R + c0.R - 1 - c0.n_win
 
     @torch.no_grad()
-    def verify(self, input_ids: torch.Tensor) -> torch.Tensor:
+    def verify(self, input_ids: torch.Tensor, logits=None) -> torch.Tensor:
         """Check n <= N_MAX_VERIFY (16) tokens [B, n] after prefill() without committing them: step()'s projections over B n rows
         (the fused GEMVs while B n <= 4), RoPE at pos .. pos + n - 1 and per layer cache.attend_verify (the decode kernels).  Returns the logits of every position [B, n, vocab]; every
         layer's n post-RoPE K / V rows are kept until accept(m) commits rows 0 .. m - 1.  Changes no cache state."""
         from .cache import N_MAX_VERIFY, _check_room
+        self._logits_refused("verify()", logits)
         self._shared_refused("verify()")
         self._kivi_refused("verify()")
         if self.tp_world > 1:
@@ -517,7 +529,7 @@ class FastGearDecoder:
         return m
 
     @torch.no_grad()
-    def verify_tree(self, input_ids: torch.Tensor, parents: torch.Tensor) -> torch.Tensor:
+    def verify_tree(self, input_ids: torch.Tensor, parents: torch.Tensor, logits=None) -> torch.Tensor:
         """verify() over a draft tree: input_ids [B, n] are the nodes' tokens (node 0 = the last committed token), parents long [n]
         or [B, n] the tree (speculative.tree_layout's form, any device).  Node i runs at RoPE position pos + depth[b, i] and attends
         over the cache and its own ancestors among the n rows (cache.attend_verify_tree).  Returns the logits of every node
@@ -525,6 +537,7 @@ class FastGearDecoder:
         verify()'s refusals; room is needed for the deepest path only.  Changes no cache state."""
         from .cache import N_MAX_VERIFY, _check_room
         from .speculative import tree_layout
+        self._logits_refused("verify_tree()", logits)
         self._shared_refused("verify_tree()")
         self._kivi_refused("verify_tree()")
         if self.tp_world > 1:
@@ -643,7 +656,7 @@ class FastGearDecoder:
 
     @torch.no_grad()
     def generate_speculative(self, input_ids: torch.Tensor, max_length: int, draft="ngram", n_draft: int = 3,
-                             return_stats: bool = False, sampling=None, tree_width: int = 1):
+                             return_stats: bool = False, sampling=None, tree_width: int = 1, logits=None):
         """Greedy decoding with speculative verification: each pass drafts k <= n_draft tokens (draft = "ngram":
         speculative.ngram_draft over the tokens so far, or a callable (tokens [B, L], k) -> [B, k]), verifies [last token, d1 .. dk]
         in one verify() and commits the accepted drafts + the model's next token (accept(a + 1)).  With batch > 1 every row commits
@@ -658,6 +671,7 @@ class FastGearDecoder:
         up to tree_width continuations of the trailing n-gram under one root), checks it in one verify_tree() pass, walks it with
         speculative.tree_accept and commits the batch's minimum path length through accept_path(), each row its own path."""
         from .speculative import accepted_lengths, ngram_draft
+        self._logits_refused("generate_speculative()", logits)
         self._kivi_refused("generate_speculative()")
         if self.shared_prefix_tokens:
             raise NotImplementedError("generate_speculative(): not implemented for a shared-prefix decoder (shared_prefix_tokens > 0)")
@@ -837,13 +851,14 @@ class FastGearDecoder:
         self._state_dirty = True
 
     def generate_beam(self, input_ids: torch.Tensor, max_length: int, num_beams: int = None, eos_token_id: int = None,
-                      length_penalty: float = 1.0, num_return_sequences: int = 1, pad_token_id: int = 0):
+                      length_penalty: float = 1.0, num_return_sequences: int = 1, pad_token_id: int = 0, logits=None):
         """Beam search with `batch` beams over ONE prompt input_ids [1, T] (a decoder built with shared_prefix_tokens > 0;
         num_beams, when given, must equal batch): prefill_shared() once, then per token log_softmax / top-2S in torch,
         reorder(beam_idx) and step().  Returns (sequences [num_return_sequences, max_length] long, padded with pad_token_id, scores
         [num_return_sequences] fp32: sum of log-probabilities / length ** length_penalty), best first.  The rule is fixed in
         gear_amd/beam.py.  Eager steps only."""
         from .beam import beam_search
+        self._logits_refused("generate_beam()", logits)
         return beam_search(self, input_ids, max_length, num_beams, eos_token_id, length_penalty, num_return_sequences, pad_token_id)
 
     # ------------------------------------------------------------------------------------------------ hipGraph decode
@@ -851,10 +866,12 @@ class FastGearDecoder:
         c = self.layers[0]["cache"]
         self.state.copy_(torch.tensor([self.pos, c.n_win, c.n_comp, c.n_win + 1], dtype=torch.int32))
 
-    def _step_body_dyn(self, sampling=None):
+    def _step_body_dyn(self, sampling=None, proc=None):
         """The token step with every per-token scalar read from self.state on the device: identical launches for every
         token, so the whole thing (embedding -> 32 layers -> lm_head -> argmax -> state advance) is one graph.  With `sampling`
-        the argmax is gear_sample_tokens at position state.pos + 1 (read on the device before the advance)."""
+        the argmax is gear_sample_tokens at position state.pos + 1 (read on the device before the advance).  With `proc` (the
+        state of _generate_processed) the token comes from the processed logits -- gear_logits_process with the history length
+        state.pos + 1 and cur = the token just fed, appended inside the launch -- and gear_eos_update follows the choice."""
         m = self.model.model
         res = m.embed_tokens(self.tok.view(-1))
         for lw in self.layers:
@@ -864,7 +881,15 @@ class FastGearDecoder:
             act = self._norm_linear(res, lw["wgu"], swiglu=True)
             res = self._linear_add(act, lw["wd"], res)
         logits = self._norm_linear(res, self.w_head)
-        if sampling is None:
+        if proc is not None:
+            src = logits
+            if proc["lp"].active:
+                src = process_logits(logits, proc["lp"], proc["hist"].buf, 1, proc["prompt_len"], cur=self.tok.view(-1),
+                                     pos_dev=self.state, out=proc["buf"])
+            self.tok.copy_(sample_tokens(src, proc["sp"], pos=1, pos_dev=self.state)[0].view(-1, 1))
+            if proc["eos"]:
+                eos_update(self.tok, proc["done"], proc["eos"], proc["pad"], proc["n_done"])
+        elif sampling is None:
             self.tok.copy_(logits.argmax(-1, keepdim=True))
         else:
             self.tok.copy_(sample_tokens(logits, sampling, pos=1, pos_dev=self.state)[0].view(-1, 1))
@@ -885,7 +910,7 @@ class FastGearDecoder:
         sequence, position) only, so the tokens equal those of eager step() + sample_tokens at self.pos."""
         return self._graph_step(token_ids, sampling)
 
-    def _graph_step(self, token_ids, sampling):
+    def _graph_step(self, token_ids, sampling, proc=None):
         if self.shared_prefix_tokens:
             raise NotImplementedError("step_graph(): not implemented for a shared-prefix decoder (shared_prefix_tokens > 0): the "
                                       "shared-prefix attention has eager steps only")
@@ -911,15 +936,19 @@ class FastGearDecoder:
             self.tok.copy_(token_ids.view(self.batch, 1))
         if sampling is not None and self.graph_sampled is not None and self._graph_sampling != sampling:
             self.graph_sampled = None        # other params: capture again
-        graph = self.graph if sampling is None else self.graph_sampled
+        if proc is not None and self.graph_proc is not None and self._graph_proc_key != proc["key"]:
+            self.graph_proc = None           # other params or other buffers: capture again
+        graph = self.graph_proc if proc is not None else self.graph if sampling is None else self.graph_sampled
         if graph is None:
             self._sync_state()
             self._state_dirty = False
             torch.cuda.synchronize()
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph):
-                logits = self._step_body_dyn(sampling)
-            if sampling is None:
+                logits = self._step_body_dyn(sampling, proc)
+            if proc is not None:
+                self.graph_proc, self._graph_proc_key, self.logits_proc_static = graph, proc["key"], logits
+            elif sampling is None:
                 self.graph, self.logits_static = graph, logits
             else:
                 self.graph_sampled, self._graph_sampling, self.logits_sampled_static = graph, sampling, logits
@@ -951,7 +980,7 @@ class FastGearDecoder:
     @torch.no_grad()
     def generate(self, input_ids: torch.Tensor, max_length: int, graph: bool = False, sampling=None,
                  shared_prefix: bool = False, suffix_ids: torch.Tensor = None, reuse_prefix: bool = False,
-                 return_logprobs: bool = False):
+                 return_logprobs: bool = False, logits=None, eos_token_id=None, pad_token_id=None, stop_check_every: int = 8):
         """Greedy decoding; with `sampling` (a sampling.SamplingParams) every token is drawn by gear_sample_tokens at its own
         position -- the first from the prefill logits, the rest from step()'s (graph=True: step_graph_sampled(), same tokens).
         shared_prefix=True (a decoder built with shared_prefix_tokens > 0): input_ids is ONE prompt [1, T], the result is
@@ -965,7 +994,26 @@ class FastGearDecoder:
         return_logprobs=True: returns (tokens, logprobs) -- logprobs fp32 [B, generated tokens], the log-softmax of each step's raw
         logits at the emitted token (before temperature / top-k / top-p: HF's compute_transition_scores on unprocessed scores),
         one gear_token_logprobs launch per step on the step's fp16 logits (graph=True: eagerly after each replay, on the graph's
-        static logits buffer; the captured graphs are unchanged).  The tokens are those of the same call without it."""
+        static logits buffer; the captured graphs are unchanged).  The tokens are those of the same call without it.
+        logits (a logits.LogitsParams): every step's raw logits go through gear_logits_process (bias / bans, repetition penalty,
+        n-gram ban, minimum length -- HF's processors in HF's order) into a buffer of their own, and the token is taken from that
+        buffer by gear_sample_tokens (greedy = temperature 0: the first-index argmax); return_logprobs keeps reading the raw
+        logits.  eos_token_id (an int or up to 8; default: logits.eos_token_id): gear_eos_update after every choice -- a row that
+        emitted an EOS id is pad_token_id (default: the first EOS id) from then on, the host reads the count of finished rows every
+        stop_check_every tokens (the one synchronisation this adds) and generation ends once every row is finished: the result
+        is [B, L <= max_length], cut behind the last row's EOS as HF's generate() cuts it.  graph=True ("gear" cache): a graph of
+        its own keyed by (sampling, logits, EOS ids, pad, buffers); the greedy and the sampled graph are left alone.  Without
+        `logits` and `eos_token_id` nothing here runs."""
+        if logits is not None and not isinstance(logits, LogitsParams):
+            raise TypeError(f"generate(): logits must be a logits.LogitsParams, got {type(logits).__name__}")
+        eos = eos_ids(eos_token_id) or (logits.eos_ids if logits is not None else ())
+        if not eos and pad_token_id is not None:
+            raise ValueError("generate(): pad_token_id without an eos_token_id")
+        if not isinstance(stop_check_every, int) or stop_check_every < 1:
+            raise ValueError(f"generate(): stop_check_every = {stop_check_every!r} must be an int >= 1")
+        processed = bool(eos) or (logits is not None and logits.active)
+        if processed and self.tp_world > 1:
+            raise NotImplementedError("generate(logits= / eos_token_id=): not implemented for head-sharded decoders (tp_world > 1)")
         if shared_prefix and graph:
             raise NotImplementedError("generate(shared_prefix=True, graph=True): shared-prefix decoding has eager steps only")
         if graph or shared_prefix:
@@ -973,6 +1021,10 @@ class FastGearDecoder:
         if (suffix_ids is not None or reuse_prefix) and not shared_prefix:
             raise ValueError("generate(): suffix_ids / reuse_prefix need shared_prefix=True")
         lps = [] if return_logprobs else None      # one [B] column of log-probs per emitted token
+        if processed:
+            toks = self._generate_processed(input_ids, max_length, graph, sampling, logits or LogitsParams(), eos, pad_token_id,
+                                            stop_check_every, shared_prefix, suffix_ids, reuse_prefix, lps)
+            return (toks, torch.stack(lps, 1)) if return_logprobs else toks
         if sampling is not None:
             toks = self._generate_sampled(input_ids, max_length, graph, sampling, shared_prefix, suffix_ids, reuse_prefix, lps)
             return (toks, torch.stack(lps, 1)) if return_logprobs else toks
@@ -1065,3 +1117,81 @@ class FastGearDecoder:
         self.check_exchange()
         self.check_block_kernel()
         return torch.cat(out, dim=1)
+
+    def _proc_begin(self, logits0, cap, sp, lp, eos, pad, prompt_ids):
+        """The buffers of a processed generation: token history [B, cap] loaded with the prompt columns, the processed-logits
+        buffer, the done flags and their count.  They are kept on the decoder while their shapes fit (the processed graph holds
+        their pointers); its key names everything the capture bakes in."""
+        B = logits0.shape[0]
+        st = self._proc_state
+        if st is None or st["hist"].cap != cap or st["buf"].shape != logits0.shape or st["buf"].dtype != logits0.dtype:
+            st = dict(hist=TokenHistory(B, cap, self.dev), buf=torch.empty_like(logits0),
+                      done=torch.zeros(B, dtype=torch.int32, device=self.dev), n_done=torch.zeros(1, dtype=torch.int32, device=self.dev))
+            st["serial"] = getattr(self, "_proc_serial", 0) + 1
+            self._proc_serial = st["serial"]
+            self._proc_state = st
+        st["done"].zero_()
+        st["n_done"].zero_()
+        n0 = st["hist"].load(prompt_ids)
+        st.update(sp=sp, lp=lp, eos=eos, pad=pad, prompt_len=n0,
+                  key=(sp, lp, eos, pad, n0 if lp.min_new_tokens else 0, st["serial"]))
+        return st
+
+    def _generate_processed(self, input_ids, max_length, graph, sampling, lp, eos, pad, every, shared_prefix=False, suffix_ids=None,
+                            reuse_prefix=False, lps=None):
+        """generate() with logits processors and / or EOS stopping: raw logits -> gear_logits_process -> gear_sample_tokens ->
+        gear_eos_update per step; the history length is self.pos (every token fed so far), the token just fed is appended by the
+        processing launch."""
+        sp = sampling if sampling is not None else SamplingParams(temperature=0.0)
+        pad = int(pad) if pad is not None else (eos[0] if eos else 0)
+        logits, out = self._generate_start(input_ids, max_length, shared_prefix, suffix_ids, reuse_prefix)
+        prompt = torch.cat([t.expand(logits.shape[0], -1) for t in out], 1)
+        if prompt.shape[1] >= max_length:
+            raise ValueError(f"generate(): the prompt ({prompt.shape[1]} tokens) leaves no room within max_length = {max_length}")
+        st = self._proc_begin(logits, max_length, sp, lp, eos, pad, prompt)
+        assert self.pos == st["prompt_len"], (self.pos, st["prompt_len"])
+
+        def choose(raw, cur):
+            src = raw
+            if lp.active:
+                src = process_logits(raw, lp, st["hist"].buf, self.pos, st["prompt_len"], cur=cur, out=st["buf"])
+            tok = sample_tokens(src, sp, pos=self.pos)[0].view(-1, 1)
+            if eos:
+                eos_update(tok, st["done"], eos, pad, st["n_done"])
+            return tok
+
+        def finished(n_new):
+            return bool(eos) and n_new % every == 0 and int(st["n_done"].item()) == st["done"].numel()
+
+        nxt = choose(logits, None)
+        self._record_logprobs(lps, logits, nxt)
+        out.append(nxt)
+        n_new, length = 1, prompt.shape[1] + 1
+        if graph and length < max_length and not finished(n_new):
+            logits = self.step(nxt)                             # one eager step warms up every library handle
+            nxt = choose(logits, nxt.view(-1))
+            self._record_logprobs(lps, logits, nxt)
+            out.append(nxt)
+            self.tok.copy_(nxt)
+            n_new, length = n_new + 1, length + 1
+        while length < max_length and not finished(n_new):
+            if graph:
+                nxt = self._graph_step(None, None, st).clone()
+                self._record_logprobs(lps, self.logits_proc_static, nxt)
+            else:
+                logits = self.step(nxt)
+                nxt = choose(logits, nxt.view(-1))
+                self._record_logprobs(lps, logits, nxt)
+            out.append(nxt)
+            n_new, length = n_new + 1, length + 1
+        self.check_exchange()
+        self.check_block_kernel()
+        toks = torch.cat(out, dim=1)
+        if eos and int(st["n_done"].item()) == st["done"].numel():
+            # every row is finished: cut behind the last row's EOS (its first EOS id among the generated tokens), as HF does
+            hit = torch.isin(toks[:, prompt.shape[1]:], torch.tensor(eos, device=toks.device))
+            keep = prompt.shape[1] + int(hit.int().argmax(1).max()) + 1
+            toks = toks[:, :keep]
+            if lps is not None:
+                del lps[keep - prompt.shape[1]:]
+        return toks

@@ -997,9 +997,21 @@ class LlamaForCausalLM_GEARKIVI(nn.Module):
 
     @torch.no_grad()
     def generate(self, input_ids, max_length: int, use_cache: bool = True, do_sample: bool = False, temperature: float = 1.0,
-                 top_k: int = 50, top_p: float = 1.0, seed: int = 0):
+                 top_k: int = 50, top_p: float = 1.0, seed: int = 0, repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0,
+                 min_new_tokens: int = 0, eos_token_id=None, pad_token_id=None):
         """Greedy by default; do_sample=True samples with HF's generate() kwargs and defaults (temperature, top_k, top_p) through
-        gear_sample_tokens (sampling.py), the token at position P drawn from the (seed, sequence, P) random stream."""
+        gear_sample_tokens (sampling.py), the token at position P drawn from the (seed, sequence, P) random stream.
+        repetition_penalty / no_repeat_ngram_size / min_new_tokens / eos_token_id / pad_token_id: HF's kwargs of those names
+        (logits.py: gear_logits_process in front of the token choice, gear_eos_update behind it); rows that emitted an EOS id are
+        pad_token_id (default: the first EOS id) from then on and the result ends behind the last row's EOS.  With their defaults
+        none of that runs."""
+        from .logits import LogitsParams
+        lp = LogitsParams(repetition_penalty, no_repeat_ngram_size, min_new_tokens, eos_token_id)
+        if lp.active or lp.eos_ids:
+            sp = SamplingParams(temperature, top_k, top_p, seed) if do_sample else SamplingParams(temperature=0.0)
+            return self._generate_processed(input_ids, max_length, sp, lp, pad_token_id)
+        if pad_token_id is not None:
+            raise ValueError("generate(): pad_token_id without an eos_token_id")
         if do_sample:
             return self._generate_sampled(input_ids, max_length, SamplingParams(temperature, top_k, top_p, seed))
         logits, past = self.forward(input_ids, None, True)
@@ -1024,3 +1036,37 @@ class LlamaForCausalLM_GEARKIVI(nn.Module):
             nxt = sample_tokens(logits[:, -1], params, pos=n)[0].view(-1, 1)
             out.append(nxt)
         return torch.cat(out, dim=1)
+
+    def _generate_processed(self, input_ids, max_length: int, sp, lp, pad, stop_check_every: int = 8):
+        """The sampled loop with the logits processors in front of the token choice and the EOS bookkeeping behind it (the same
+        three launches per step as FastGearDecoder.generate(logits=...))."""
+        from .logits import TokenHistory, eos_update, process_logits
+        B, n = input_ids.shape
+        if n >= max_length:
+            raise ValueError(f"generate(): the prompt ({n} tokens) leaves no room within max_length = {max_length}")
+        eos = lp.eos_ids
+        pad = int(pad) if pad is not None else (eos[0] if eos else 0)
+        dev = input_ids.device
+        hist = TokenHistory(B, max_length, dev)
+        n0 = hist.load(input_ids)
+        done = torch.zeros(B, dtype=torch.int32, device=dev)
+        n_done = torch.zeros(1, dtype=torch.int32, device=dev)
+        logits, past = self.forward(input_ids, None, True)
+        out, cur = [input_ids], None
+        while True:
+            raw = logits[:, -1]
+            src = process_logits(raw, lp, hist, n, n0, cur=cur) if lp.active else raw
+            nxt = sample_tokens(src, sp, pos=n)[0].view(-1, 1)
+            if eos:
+                eos_update(nxt, done, eos, pad, n_done)
+            out.append(nxt)
+            if n + 1 >= max_length or (eos and (n + 1 - n0) % stop_check_every == 0 and int(n_done.item()) == B):
+                break
+            logits, past = self.forward(nxt, past, True)
+            n += 1
+            cur = nxt.view(-1)
+        toks = torch.cat(out, dim=1)
+        if eos and int(n_done.item()) == B:
+            hit = torch.isin(toks[:, n0:], torch.tensor(eos, device=dev))
+            toks = toks[:, :n0 + int(hit.int().argmax(1).max()) + 1]
+        return toks

@@ -89,6 +89,18 @@ def run(variant, args, dev):
         sampling = SamplingParams(args.temperature, args.top_k, args.top_p, args.seed)
         hook_kw = dict(do_sample=True, temperature=args.temperature, top_k=args.top_k, top_p=args.top_p, seed=args.seed)
     fast_kw = {} if sampling is None else dict(sampling=sampling)
+    # --repetition_penalty / --no_repeat_ngram_size / --min_new_tokens / --stop_at_eos: HF's generate() kwargs of those names through
+    # gear_logits_process and gear_eos_update (random weights: the EOS id is whatever --stop_at_eos names)
+    eos = None if args.stop_at_eos < 0 else args.stop_at_eos
+    if args.repetition_penalty != 1.0 or args.no_repeat_ngram_size or args.min_new_tokens or eos is not None:
+        from gear_amd.logits import LogitsParams
+        fast_kw["logits"] = LogitsParams(args.repetition_penalty, args.no_repeat_ngram_size, args.min_new_tokens, eos)
+        if args.graph:
+            fast_kw["graph"] = True
+        hook_kw.update(repetition_penalty=args.repetition_penalty, no_repeat_ngram_size=args.no_repeat_ngram_size,
+                       min_new_tokens=args.min_new_tokens, eos_token_id=eos)
+    elif args.graph:
+        fast_kw["graph"] = True
     cache_bytes = None
     if variant == "gearl" and args.fast and args.shared_prefix:
         # the batch continues ONE prompt (row 0) stored once: a batch-1 prefix cache + per-sequence tails (gear_attn_decode_shared)
@@ -216,7 +228,20 @@ def main():
     ap.add_argument("--top_k", type=int, default=50)
     ap.add_argument("--top_p", type=float, default=0.95)
     ap.add_argument("--seed", type=int, default=0, help="key of the sampler's random stream")
+    # logits processors and EOS stopping (HF's generate() kwargs; the reference evaluates through them: evaluation_bbh_cot.py:374-392)
+    ap.add_argument("--repetition_penalty", type=float, default=1.0, help="HF's repetition_penalty (1: off)")
+    ap.add_argument("--no_repeat_ngram_size", type=int, default=0, help="HF's no_repeat_ngram_size (0: off)")
+    ap.add_argument("--min_new_tokens", type=int, default=0, help="EOS is held back for this many tokens (needs --stop_at_eos)")
+    ap.add_argument("--stop_at_eos", type=int, default=-1, metavar="EOS_ID",
+                    help="stop a row at this token id and pad it from there; generation ends once every row stopped (-1: off)")
+    ap.add_argument("--graph", action="store_true", help="with --fast --model gearl: captured token steps (generate(graph=True))")
     args = ap.parse_args()
+    if args.graph and (not args.fast or args.shared_prefix or args.tree_width or args.all or "gearl" not in args.model):
+        raise SystemExit("--graph needs --fast --model gearl without --shared_prefix / --tree_width / --all (graph steps run on the "
+                         "compressed cache)")
+    if (args.tree_width or args.num_beams) and (args.repetition_penalty != 1.0 or args.no_repeat_ngram_size or args.min_new_tokens
+                                                or args.stop_at_eos >= 0):
+        raise SystemExit("the logits processors / --stop_at_eos run in generate() only (not with --tree_width or --num_beams)")
     if args.shared_prefix and not args.fast:
         raise SystemExit("--shared_prefix needs --fast (shared-prefix decoding lives in FastGearDecoder)")
     if args.num_beams and not (args.fast and args.shared_prefix):

@@ -707,6 +707,56 @@ int gear_token_logprobs(const void* logits, const void* ref_logits, const int64_
                         float* lp, float* lse, int32_t* rank, float* kl, int32_t* agree, int32_t* top_idx, float* top_lp,
                         void* stream);
 
+/* ---- logits processors and EOS bookkeeping for the decoders (csrc/logits.hip) -------------------------------------------------
+ * What HF's generate() applies between lm_head and the token choice (the reference evaluates through it:
+ * GenerationBench/GenerationTest/evaluation_bbh_cot.py:374-392), as ONE launch per step with one workgroup per row.  Neither
+ * entry point synchronises or allocates: both are graph-capturable.
+ *
+ * The processing launch:
+ *   logits  fp16 [B, V] (fp32 when logits_fp32), row pitch ld >= V elements; 1 <= V <= 262144
+ *   out     the same type, row pitch ld_out >= V; may be the very pointer `logits` (with ld_out == ld), never a partial overlap
+ *   hist    int32 [B, hist_cap]: prompt + generated tokens of every sequence; the live length is n = pos0 + *pos_dev (pos_dev: a
+ *           device int32, e.g. the decode state {pos, ...}; NULL: n = pos0), clamped to [0, hist_cap]
+ *   cur     optional int64 [B]: the token just fed.  It is stored at hist[b][n - 1] by one lane (a plain vector store) in front of a
+ *           workgroup barrier, and the launch itself reads entry n - 1 from cur: the history grows inside a captured step
+ *   prompt_len  length of the prompt part of the history (min_new_tokens counts n - prompt_len)
+ *   params  (host pointer) repetition_penalty > 0 (1: off), no_repeat_ngram >= 0 (0: off), min_new_tokens >= 0, n_eos <= 8 EOS ids
+ *           inline, n_bias pairs {int32 token, float bias} in DEVICE memory with unique tokens (a bias of -inf is a ban)
+ * Per row, in HF's processor order, with x_j = fp32(logits[j]):
+ *   1. bias     x_t += bias for every pair (SequenceBiasLogitsProcessor with length-1 sequences)
+ *   2. penalty  once for every distinct token of hist[b][0 .. n): x < 0 ? x * p : x / p (RepetitionPenaltyLogitsProcessor) -- the
+ *               history marks an LDS bitmap of V bits with atomicOr, so duplicates cannot apply it twice
+ *   3. bans     x = -inf: with g = no_repeat_ngram and n >= g, hist[i + g - 1] for every i whose g - 1 tokens hist[i .. i + g - 1)
+ *               equal the last g - 1 tokens hist[n - g + 1 .. n) (NoRepeatNGramLogitsProcessor; g = 1 bans every seen token);
+ *               every EOS id while n - prompt_len < min_new_tokens (MinNewTokensLengthLogitsProcessor)
+ * out[j] = the value rounded ONCE to the output type (fp32 arithmetic, IEEE division).  An entry no processor touches comes out
+ * with the bits it came in with (also -0, NaN payloads); -inf stays -inf.  History, EOS and bias ids outside [0, V) are skipped and
+ * never index anything.  Nothing is read or written past column V - 1 of a row or past entry n - 1 of a history.  Rows that start
+ * on a 16-byte boundary (input and output) move in 16-byte vectors, other rows (an odd pitch, a sliced view) in the widest
+ * accesses their alignment allows -- the same bits either way.
+ * Refused with a status < 0 and a gear_last_error message before any launch: null logits / out / hist / params, V <= 0 or
+ * V > 262144, ld < V or ld_out < V, B < 0, a penalty that is <= 0 or NaN, no_repeat_ngram < 0, min_new_tokens < 0, n_eos outside
+ * [0, 8], n_bias < 0 or n_bias > 0 with a null table, pos0 < 0, hist_cap <= 0.  B == 0 returns 0 without a launch.
+ *
+ * The EOS launch (after the token choice): tok int64 [B] and done int32 [B] are read and written -- a row with done[b] != 0 gets
+ * tok[b] = pad; otherwise, if tok[b] is one of the n_eos <= 8 ids (host array), done[b] = 1 and the EOS token itself stays.
+ * *n_done (device int32) = the number of rows with done != 0 after the update (integer sums, merged in wave order).  One
+ * workgroup.  Refused: null tok / done / n_done, B < 0, n_eos outside [0, 8], n_eos > 0 with null ids; B == 0 returns 0. */
+typedef struct {
+    float repetition_penalty;
+    int no_repeat_ngram;
+    int min_new_tokens;
+    int n_eos;
+    int eos[8];
+    int n_bias;
+    int reserved;
+    const void* bias;
+} gear_logits_params;
+int gear_logits_process(const void* logits, void* out, int logits_fp32, int B, int V, int64_t ld, int64_t ld_out, int32_t* hist,
+                        int hist_cap, const int* pos_dev, int pos0, const int64_t* cur, int prompt_len,
+                        const gear_logits_params* p, void* stream);
+int gear_eos_update(int64_t* tok, int32_t* done, int B, const int* eos, int n_eos, int64_t pad, int32_t* n_done, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
